@@ -7,7 +7,14 @@ synthetic batch (config 2) + one decode pass over the Huffman payload of a
 1M-string batch (config 3), both through the C-ABI (libqhuff.so).  value =
 (raw bytes encoded + raw bytes decoded, summed over ranks) / wall time.
 
-Run: python bench.py [--gpus N --steps K --warmup W].  One process per GPU:
+Run: python bench.py [--gpus N --steps K --warmup W].  A plain run sets up,
+warms up, times the K steps and prints the result line (the kernel times and
+roofline in it come from launches of the timed steps themselves).  --full adds
+the legs that take runs of their own, none of them `value`: header hashing,
+two streams, the real-workload batches, the PCIe-inclusive host path and the
+CPU baseline (each still switchable: --no-overlap, --no-workloads,
+--no-host-path, --cpu-seconds 0).  --dump-outputs DIR writes what the last
+timed step computed (dump_outputs).  One process per GPU:
 under torch.distributed.run (WORLD_SIZE must equal --gpus), or, with no
 launcher, bench.py starts the N rank processes itself before anything touches
 the GPU (ranks beyond the visible GPUs share them round-robin).  Strings are
@@ -37,13 +44,24 @@ sys.path.insert(0, os.path.join(ROOT, "ls-qpack_amd"))
 METRIC = ("GB/s device-resident QPACK Huffman enc+dec, 1M-string batch, "
           "1/2/4/8 MI355X")
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
+DUMP_BUDGET = 56 * 10 ** 6  # --dump-outputs: bytes over all files (< 64 MB)
+DUMP_SEED = 0x51A7
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: "
+                         "header hashing, two streams, real workloads, host "
+                         "path, CPU baseline (never `value`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "outputs as DIR/<name>.npy (float32 / float64; a "
+                         "fixed seeded sample of an array too large for its "
+                         "share of 56 MB)")
     ap.add_argument("--n", type=int, default=1 << 20,
                     help="strings per GPU (default 1M)")
     ap.add_argument("--copies", type=int, default=4)
@@ -82,7 +100,32 @@ def parse():
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles",
                                                   "pmc_latest.json"),
                     help="PMC traffic summary (tools/pmc_summary.py)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def dump_sample(np, size, cap):
+    """Indices of the elements --dump-outputs keeps of a `size`-element
+    array allowed `cap` elements: all of them, or a sorted sample drawn from
+    a fixed seed (a function of size and cap alone, so two builds given the
+    same arguments keep the same elements)."""
+    if size <= cap:
+        return None
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.integers(0, size, cap))
+
+
+def dump_outputs(np, out_dir, arrays, suffix=""):
+    """--dump-outputs: `arrays` maps a name to (array, dtype); each is
+    written as out_dir/<name><suffix>.npy in that dtype (float32 holds a
+    byte exactly, float64 an offset).  The files share DUMP_BUDGET bytes
+    evenly; an array beyond its share is sampled (dump_sample)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for name, (a, dt) in arrays.items():
+        idx = dump_sample(np, a.size, share // np.dtype(dt).itemsize)
+        if idx is not None:
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a.astype(dt))
 
 
 def cpu_model():
@@ -170,27 +213,28 @@ def launch_plan(gpus, env, port):
     return plan
 
 
-def self_launch(gpus):
+def self_launch(gpus, argv=None):
     """`bench.py --gpus N` without an outside launcher: start N rank
     processes (this process has not touched the GPU, and never does), wait
     for them, exit with the worst status.  Rank 0 prints the JSON line."""
     import subprocess
     plan = launch_plan(gpus, os.environ, free_port())
     procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__)]
-                              + sys.argv[1:], env=e) for e in plan]
+                              + list(sys.argv[1:] if argv is None else argv),
+                              env=e) for e in plan]
     rcs = [p.wait() for p in procs]
     bad = [rc for rc in rcs if rc != 0]
     sys.exit(bad[0] if bad else 0)
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     if args.config4:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             sys.exit("bench: --config4 is one process driving --gpus devices "
                      "(one host thread each); do not start it per rank")
     elif rank_check(args.gpus, os.environ) is None:
-        return self_launch(args.gpus)
+        return self_launch(args.gpus, argv)
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -325,6 +369,22 @@ def main():
     # launch that raised one produced no valid output
     dev_err = codec.device_error()
 
+    if args.dump_outputs:
+        # what a caller of the last timed step received: the encode call's
+        # bytes and offsets, the decode call's bytes, offsets and statuses
+        last = args.warmup + args.steps - 1
+        k = last % args.copies
+        j = (last + args.copies // 2) % args.copies
+        eoff = e_off[k].cpu().numpy().view(np.uint32)
+        ooff = d_ooff[j].cpu().numpy().view(np.uint32)
+        dump_outputs(np, args.dump_outputs, {
+            "enc_out": (e_out[k][:int(eoff[-1])].cpu().numpy(), np.float32),
+            "enc_out_off": (eoff, np.float64),
+            "dec_out": (d_out[j][:int(ooff[-1])].cpu().numpy(), np.float32),
+            "dec_out_off": (ooff, np.float64),
+            "dec_status": (d_st[j].cpu().numpy(), np.float32),
+        }, suffix="" if rank == 0 else "_rank%d" % rank)
+
     if world > 1:
         t = torch.tensor([wall, 0.0 if ok_dec else 1.0, float(dev_err)],
                          dtype=torch.float64)
@@ -378,57 +438,25 @@ def main():
     if pmc_src:
         roof["traffic_source"] = pmc_src
 
-    # ---- header hashing, outside the timed step --------
-    # the batch read as n/2 (name, value) headers: XXH32 name + name/value
-    hh = n // 2
-    h1 = torch.empty(hh, dtype=torch.int32, device=dev)
-    h2 = torch.empty(hh, dtype=torch.int32, device=dev)
-    # timed the way enc/dec are: each launch's own dispatch timestamps
-    for i in range(10):
-        codec.xxh32_headers_into(d_in[i % args.copies], d_off[i % args.copies],
-                                 hh, qhuff.XXH_SEED, h1, h2, stream)
-    codec.timing(True)
-    nh = max(1, min(args.steps, 20))
-    for i in range(nh):
-        codec.xxh32_headers_into(d_in[i % args.copies], d_off[i % args.copies],
-                                 hh, qhuff.XXH_SEED, h1, h2, stream)
-    ht = [u for k, u in codec.timing_read() if k == qhuff.KIND_HASH]
-    codec.timing(False)
-    hash_ms = sum(ht) / len(ht) * 1e-3
-    hash_bytes = int(off[2 * hh])
-    hash_alg = hash_bytes + 4 * (2 * hh + 1) + 8 * hh
-    hashing = {"kernel": "qhuff_hash_kernel", "headers": hh,
-               "kernel_us": round(hash_ms * 1e3, 2),
-               "timing": "mean over %d launches, dispatch-stamped HIP "
-                         "events (hipExtLaunchKernel)" % len(ht),
-               "payload_gbps": round(hash_bytes / (hash_ms * 1e-3) / 1e9, 2),
-               "alg_bytes": hash_alg,
-               "roofline_frac": round(hash_alg / (hash_ms * 1e-3) / 1e9
-                                      / HBM_PEAK_GBS, 4),
-               "traffic": None}
-    if os.path.exists(args.pmc):
-        try:
-            ent = json.load(open(args.pmc)).get("kernels", {}).get(
-                "qhuff_hash_kernel")
-            if ent and ent.get("n") == hh:
-                hashing["traffic"] = ent.get("hbm_bytes_per_launch")
-        except Exception:
-            pass
+    hashing = None
+    if args.full:
+        hashing = run_hashing(args, torch, qhuff, codec, dev, stream, n, off,
+                              d_in, d_off)
 
     overlap = None
-    if args.overlap and rank == 0 and world == 1:
+    if args.full and args.overlap and rank == 0 and world == 1:
         overlap = run_overlap(args, np, torch, qhuff, dev, n, raw_bytes, d_in,
                               d_off, e_out, e_off, d_hin, d_hoff, d_out,
                               d_ooff, d_st, ms_per_step)
 
     work = None
-    if args.workloads and rank == 0 and world == 1:
+    if args.full and args.workloads and rank == 0 and world == 1:
         work = run_workloads(args, np, torch, qhuff, codec, dev, stream, n,
                              raw_bytes, enc_ms, dec_ms,
                              (d_in[0], d_off[0], d_hin[0], d_hoff[0]))
 
     host = None
-    if args.host_path and rank == 0:
+    if args.full and args.host_path and rank == 0:
         # result buffers allocated and faulted in once (a fresh np.zeros of
         # the bound per call would time page faults, not the library); the
         # first calls size the pinned / device staging buffers; time after
@@ -489,7 +517,7 @@ def main():
     # an idle GPU before a leg slow its first launches (the hash leg's mean
     # read 16.5 us against rocprof's 12.5 when it ran after this one) -------
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args, data, off, h_np, h_off_np, n, raw_bytes)
 
     if rank == 0:
@@ -497,7 +525,7 @@ def main():
             "metric": METRIC, "value": round(value, 3), "unit": "GB/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "full": args.full, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
             "data": "synthetic (xorshift64 %s alphabet, U[8,64] B strings)"
                     % args.alphabet,
             "config": {"workload": "config2+3: encode 1M strings + decode 1M "
@@ -511,9 +539,10 @@ def main():
             "dec_payload_gbps": round(raw_bytes / (dec_ms * 1e-3) / 1e9, 2),
             "roundtrip_ok": bool(ok_dec),
             "device_error": dev_err,
-            "xxh32_headers": hashing,
             "roofline": roof, "cpu_baseline": cpu,
         }
+        if hashing:
+            line["xxh32_headers"] = hashing
         if host:
             line["host_path"] = host
         if work:
@@ -527,6 +556,46 @@ def main():
     if dev_err or not ok_dec:
         sys.exit("bench: device error %d / round trip %s: the line above is "
                  "not a valid measurement" % (dev_err, ok_dec))
+
+
+def run_hashing(args, torch, qhuff, codec, dev, stream, n, off, d_in, d_off):
+    """Header hashing, a leg of its own; never `value`."""
+    # the batch read as n/2 (name, value) headers: XXH32 name + name/value
+    hh = n // 2
+    h1 = torch.empty(hh, dtype=torch.int32, device=dev)
+    h2 = torch.empty(hh, dtype=torch.int32, device=dev)
+    # timed the way enc/dec are: each launch's own dispatch timestamps
+    for i in range(10):
+        codec.xxh32_headers_into(d_in[i % args.copies], d_off[i % args.copies],
+                                 hh, qhuff.XXH_SEED, h1, h2, stream)
+    codec.timing(True)
+    nh = max(1, min(args.steps, 20))
+    for i in range(nh):
+        codec.xxh32_headers_into(d_in[i % args.copies], d_off[i % args.copies],
+                                 hh, qhuff.XXH_SEED, h1, h2, stream)
+    ht = [u for k, u in codec.timing_read() if k == qhuff.KIND_HASH]
+    codec.timing(False)
+    hash_ms = sum(ht) / len(ht) * 1e-3
+    hash_bytes = int(off[2 * hh])
+    hash_alg = hash_bytes + 4 * (2 * hh + 1) + 8 * hh
+    hashing = {"kernel": "qhuff_hash_kernel", "headers": hh,
+               "kernel_us": round(hash_ms * 1e3, 2),
+               "timing": "mean over %d launches, dispatch-stamped HIP "
+                         "events (hipExtLaunchKernel)" % len(ht),
+               "payload_gbps": round(hash_bytes / (hash_ms * 1e-3) / 1e9, 2),
+               "alg_bytes": hash_alg,
+               "roofline_frac": round(hash_alg / (hash_ms * 1e-3) / 1e9
+                                      / HBM_PEAK_GBS, 4),
+               "traffic": None}
+    if os.path.exists(args.pmc):
+        try:
+            ent = json.load(open(args.pmc)).get("kernels", {}).get(
+                "qhuff_hash_kernel")
+            if ent and ent.get("n") == hh:
+                hashing["traffic"] = ent.get("hbm_bytes_per_launch")
+        except Exception:
+            pass
+    return hashing
 
 
 def cpu_baseline(args, data, off, h_np, h_off_np, n, raw_bytes):
@@ -841,6 +910,15 @@ def run_config4(args, np, torch, qhuff):
     status_ok = all(not s["status"][:s["n"]].cpu().numpy().any()
                     for s in dec_sh[k])
     dev_err = max(c.device_error() for c in codecs)
+    if args.dump_outputs:
+        dump_outputs(np, args.dump_outputs, {
+            "enc_out": (enc_m, np.float32),
+            "enc_out_off": (enc_moff, np.float64),
+            "dec_out": (dec_m, np.float32),
+            "dec_out_off": (dec_moff, np.float64),
+            "dec_status": (cat([s["status"][:s["n"]].cpu().numpy()
+                                for s in dec_sh[k]]), np.float32),
+        })
     for c in codecs:
         c.close()
     torch.cuda.set_device(0)

@@ -448,7 +448,7 @@ def main():
 
     # fixtures written by the other generator (make_xxh32_golden.py) keep
     # their manifest lines
-    others = [fn for fn in ("xxh32.json",)
+    others = [fn for fn in ("xxh32.json", "xxh32_differential.json")
               if os.path.exists(os.path.join(HERE, fn))]
     man = []
     for fn in sorted(list(out) + copied + others):

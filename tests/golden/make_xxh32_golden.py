@@ -13,6 +13,9 @@ Vectors:
     (tests/golden/data/*.qif) hashed the way lsqpack.c:1681-1685 does:
     name_hash = XXH32(name, LSQPACK_XXH_SEED),
     nameval_hash = XXH32(value, name_hash).
+Also tests/golden/xxh32_differential.json: the reference's XXH32 of the 3000
+random (string, seed) inputs of tests/test_xxh32.py's differential test
+(differential_inputs below), so that test runs where oracle/_ref is absent.
 Usage: python tests/golden/make_xxh32_golden.py
 """
 import ctypes as C
@@ -28,6 +31,36 @@ import qpack_frames as Q  # noqa: E402
 
 SEED = 39378473
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libxxh32_ref.so")
+
+
+def differential_inputs():
+    """The (string, seed) inputs of test_oracle_differential_vs_compiled_
+    reference, from a fixed seed."""
+    rng = random.Random(7)
+    out = []
+    for _ in range(3000):
+        s = bytes(rng.randrange(256) for _ in range(rng.randrange(200)))
+        out.append((s, rng.randrange(1 << 32)))
+    return out
+
+
+def inputs_digest(inputs):
+    import hashlib
+    h = hashlib.sha256()
+    for s, seed in inputs:
+        h.update(b"%d:%d:" % (len(s), seed) + s)
+    return h.hexdigest()
+
+
+def manifest_line(name):
+    import hashlib
+    man = os.path.join(HERE, "MANIFEST.sha256")
+    with open(os.path.join(HERE, name), "rb") as f:
+        line = "%s  %s\n" % (hashlib.sha256(f.read()).hexdigest(), name)
+    with open(man) as f:
+        lines = [x for x in f if not x.rstrip().endswith("  " + name)]
+    with open(man, "w") as f:
+        f.writelines(sorted(lines + [line], key=lambda x: x.split()[1]))
 
 
 def main():
@@ -67,14 +100,15 @@ def main():
            "seed": SEED, "strings": strings, "headers": headers}
     with open(os.path.join(HERE, "xxh32.json"), "w") as f:
         json.dump(out, f, separators=(",", ":"))
-    import hashlib
-    man = os.path.join(HERE, "MANIFEST.sha256")
-    with open(os.path.join(HERE, "xxh32.json"), "rb") as f:
-        line = "%s  xxh32.json\n" % hashlib.sha256(f.read()).hexdigest()
-    with open(man) as f:
-        lines = [x for x in f if not x.rstrip().endswith("  xxh32.json")]
-    with open(man, "w") as f:
-        f.writelines(sorted(lines + [line], key=lambda x: x.split()[1]))
+    manifest_line("xxh32.json")
+    inputs = differential_inputs()
+    diff = {"source": out["source"],
+            "inputs": "make_xxh32_golden.differential_inputs()",
+            "inputs_sha256": inputs_digest(inputs),
+            "xxh32": [L.XXH32(s, len(s), seed) for s, seed in inputs]}
+    with open(os.path.join(HERE, "xxh32_differential.json"), "w") as f:
+        json.dump(diff, f, separators=(",", ":"))
+    manifest_line("xxh32_differential.json")
     print("%d strings, %d headers" % (len(strings), len(headers)))
 
 

@@ -11,6 +11,7 @@ import ctypes as C
 import json
 import os
 import random
+import sys
 
 import numpy as np
 import pytest
@@ -57,17 +58,26 @@ def test_oracle_matches_reference_headers():
     assert np.array_equal(o1, h1) and np.array_equal(o2, h2)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO),
-                    reason="oracle/_ref not built (reference not mounted)")
 def test_oracle_differential_vs_compiled_reference():
-    L = C.CDLL(REF_SO)
-    L.XXH32.restype = C.c_uint
-    L.XXH32.argtypes = [C.c_char_p, C.c_size_t, C.c_uint]
-    rng = random.Random(7)
-    for _ in range(3000):
-        s = bytes(rng.randrange(256) for _ in range(rng.randrange(200)))
-        seed = rng.randrange(1 << 32)
-        assert O.xxh32(s, seed) == L.XXH32(s, len(s), seed)
+    """3000 random (string, seed) inputs: the oracle against the reference's
+    recorded outputs for them (tests/golden/xxh32_differential.json), and
+    against the compiled reference itself where oracle/_ref is built."""
+    sys.path.insert(0, G)
+    import make_xxh32_golden as M
+    inputs = M.differential_inputs()
+    with open(os.path.join(G, "xxh32_differential.json")) as f:
+        rec = json.load(f)
+    assert M.inputs_digest(inputs) == rec["inputs_sha256"]
+    assert len(rec["xxh32"]) == len(inputs) == 3000
+    L = None
+    if os.path.exists(REF_SO):
+        L = C.CDLL(REF_SO)
+        L.XXH32.restype = C.c_uint
+        L.XXH32.argtypes = [C.c_char_p, C.c_size_t, C.c_uint]
+    for (s, seed), want in zip(inputs, rec["xxh32"]):
+        assert O.xxh32(s, seed) == want
+        if L is not None:
+            assert L.XXH32(s, len(s), seed) == want
 
 
 # ---- GPU: the HIP kernel through the C-ABI --------------------------------

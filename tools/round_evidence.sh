@@ -15,12 +15,12 @@ echo "== smoke"
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $o/smoke.log 2>&1
 rc=$?; tail -1 $o/smoke.log; fatal $rc
 echo "== bench"
-timeout -k 10 300 python -u bench.py > $o/bench.json 2> $o/bench.err
+timeout -k 10 300 python -u bench.py --full > $o/bench.json 2> $o/bench.err
 rc=$?; head -c 600 $o/bench.json; echo; fatal $rc
 echo "== bench config 4"
 timeout -k 10 300 python -u bench.py --config4 --steps 20 --warmup 5 > $o/bench_config4.json 2> $o/bench_config4.err
 rc=$?; head -c 400 $o/bench_config4.json; echo; fatal $rc
-B="bench.py --steps 20 --warmup 5 --cpu-seconds 0 --no-host-path --no-workloads --no-overlap"
+B="bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 --no-host-path --no-workloads --no-overlap"
 echo "== rocprof kernel stats"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/trace -o run -- python $B > $o/trace_bench.json 2> $o/trace.log
 rc=$?; fatal $rc
