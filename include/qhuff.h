@@ -22,6 +22,20 @@
  *   out     packed outputs; out_off (n + 1 entries) is written by the call:
  *           output i is out[out_off[i] .. out_off[i+1]), out_off[0] = 0.
  *
+ * Buffer contract (every batch call, device or host memory; enforced by
+ * tests/test_buffer_contract.py).  The pointers need no alignment beyond
+ * their types' (uint32 arrays 4 bytes, byte buffers none).
+ *   Writes: out[0 .. out_off[n]), out_off[0 .. n], status[0 .. n) (decode)
+ *           and n words of each hash output -- nothing else.  Bytes of `out`
+ *           past out_off[n] are not written, on any path: the bound sizes
+ *           the buffer, the call does not scribble in its slack.  For
+ *           n = 0 only out_off[0] (= 0) is written.
+ *   Reads:  in[in_off[0] .. in_off[n]) and in_off[0 .. n].  The kernels
+ *           load the 16-byte-aligned blocks that contain those input bytes,
+ *           so up to 15 bytes before in + in_off[0] and after in + in_off[n]
+ *           are read as well; those bytes never affect a result.  Nothing
+ *           the call reads is written.
+ *
  * Results are bit-exact with the reference functions named on each call.
  * Failure is loud: a call returns a negative QHUFF_E* code, and the library
  * has no CPU fallback -- without a usable gfx950 device qhuff_open fails.
@@ -98,11 +112,15 @@ int qhuff_open(int device, qhuff_ctx **ctx_out);
 void qhuff_close(qhuff_ctx *ctx);
 
 /* Worst-case output bytes for an encode batch of n strings totalling
- * in_bytes (30-bit longest code, + framing for LITERAL modes). */
+ * in_bytes: ceil(30 * in_bytes / 8) + n (30-bit longest code, each string
+ * rounded up to a byte), + 6 * n in the LITERAL modes (the longest prefixed
+ * length), + 16.  The 16 bytes are slack of the bound, not space the call
+ * uses (see the buffer contract above). */
 uint64_t qhuff_encode_bound(uint64_t in_bytes, uint32_t n, unsigned mode);
 
 /* Worst-case output bytes for a decode batch (5-bit shortest code,
- * lsqpack.c:5072): floor(8 * in_bytes / 5). */
+ * lsqpack.c:5072): floor(8 * in_bytes / 5) + 16 (slack, as above; n is not
+ * used). */
 uint64_t qhuff_decode_bound(uint64_t in_bytes, uint32_t n);
 
 /* Encode n strings (device pointers).
@@ -324,7 +342,8 @@ int qhuff_scan_encoder_stream(const uint8_t *buf, size_t len,
 int qhuff_dec_int(const uint8_t *buf, size_t len, unsigned prefix_bits,
                   uint64_t *value, size_t *consumed);
 
-/* Output bytes qhuff_decode_literals_host may write for these literals. */
+/* Output bytes qhuff_decode_literals_host may write for these literals:
+ * floor(8 * len / 5) per Huffman literal, len per raw one, + 16 (slack). */
 uint64_t qhuff_literals_bound(const struct qhuff_literal *lits, uint32_t n);
 
 /* Decode n literals whose payloads lie in host buffer `buf` (lits[i].pos is
@@ -480,7 +499,9 @@ int qhuff_shard_cuts(const uint32_t *in_off, uint32_t n, uint32_t g,
  * qhuff_encode_batch_host / qhuff_decode_batch_host on one context, and the
  * same bytes (out_off is global).  Each shard's uploads, kernels and
  * downloads run unsynchronised; only its copies into `out` wait for the
- * earlier shards' totals.  Synchronous. */
+ * earlier shards' totals.  (Registered buffers, qhuff_host_register: the
+ * shards write `out` directly only when the whole call's bound lies in one
+ * registered range.)  Synchronous. */
 int qhuff_encode_batch_host_multi(qhuff_ctx *const *ctxs, uint32_t g,
                                   const uint8_t *in, const uint32_t *in_off,
                                   uint32_t n, unsigned mode, uint8_t *out,

@@ -120,7 +120,9 @@ xxh32(const R &r, uint32_t a, uint32_t len, uint32_t seed)
     else
         h = seed + kP5;
     h += len;
-    while (p + 4 <= end)
+    // (end - p, not p + 4: in global memory p is the input offset itself,
+    // and p + 4 wraps for a string that ends within 4 bytes of 2^32)
+    while (end - p >= 4)
     {
         h += r.word(p) * kP3;
         h = rotl32(h, 17) * kP4;

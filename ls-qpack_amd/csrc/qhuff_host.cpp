@@ -1339,7 +1339,7 @@ static int
 host_batch(qhuff_ctx *c, bool enc, const uint8_t *in, const uint32_t *in_off,
            uint32_t n, unsigned mode, uint8_t *out, uint32_t *out_off,
            uint8_t *status, ShardSync *sync = nullptr, unsigned shard = 0,
-           bool last_shard = true)
+           bool last_shard = true, bool out_reg = false)
 {
     if (!c || !in_off || !out_off || (n && (!in || !out)) || (!enc && n && !status))
         return QHUFF_EINVAL;
@@ -1396,9 +1396,13 @@ host_batch(qhuff_ctx *c, bool enc, const uint8_t *in, const uint32_t *in_off,
     // directly, no staging copy
     const bool din = host_registered(in + a0, in_bytes)
                   && host_registered(in_off, 4ull * (n + 1));
+    // (a shard of a multi-context call writes at out + its base, beyond its
+    // own bound from `out`: out_reg is host_multi's verdict over the whole
+    // call's bound, the range the shards can write)
     const bool dout = !small
-        && host_registered(out, enc ? qhuff_encode_bound(in_bytes, n, mode)
-                                    : qhuff_decode_bound(in_bytes, n))
+        && (sync ? out_reg
+                 : host_registered(out, enc ? qhuff_encode_bound(in_bytes, n, mode)
+                                            : qhuff_decode_bound(in_bytes, n)))
         && host_registered(out_off, 4ull * (n + 1))
         && (enc || host_registered(status, n));
 
@@ -1696,11 +1700,16 @@ host_multi(qhuff_ctx *const *ctxs, uint32_t g, bool enc, const uint8_t *in,
     if (rc)
         return rc;
     ShardSync sync(g);
+    // direct DMA into `out` only if the whole call's bound is registered:
+    // shard k's bytes land at out + base[k], anywhere inside it
+    const bool out_reg = host_registered(
+        out, enc ? qhuff_encode_bound(bytes, n, mode)
+                 : qhuff_decode_bound(bytes, n));
     return run_shards(g, [&](uint32_t k) -> int {
         const uint32_t s0 = cuts[k], m = cuts[k + 1] - s0;
         const int r = host_batch(ctxs[k], enc, in, in_off + s0, m, mode, out,
                                  out_off + s0, status ? status + s0 : nullptr,
-                                 &sync, k, k + 1 == g);
+                                 &sync, k, k + 1 == g, out_reg);
         if (r)
             sync.fail();
         return r;

@@ -164,5 +164,10 @@ def test_device_multi_rebase(codecs, batches, g):
                         for k, s in enumerate(dsh)])
     assert np.array_equal(d, data)
     assert not any(s["status"][:s["n"]].cpu().numpy().any() for s in dsh)
+    # every shard's closing entry is rebased too: the next shard's base
+    for sh, bs in ((shards, base), (dsh, dbase)):
+        for k, s in enumerate(sh):
+            last = s["out_off"][-1:].cpu().numpy().view(np.uint32)
+            assert int(last[0]) == bs[k + 1]
     for c in codecs[:g]:
         assert c.device_error() == 0
