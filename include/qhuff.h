@@ -279,6 +279,76 @@ struct qhuff_decode_retval
 qhuff_huff_decode(qhuff_ctx *ctx, const unsigned char *src, int src_len,
                   unsigned char *dst, int dst_len);
 
+/* ---- batched resumable decode: strings continued across chunks --------
+ * The reference decodes a literal that straddles two stream reads with its
+ * second, resumable decoder: every lsqpack_huff_decode call that is not
+ * `resume == 0 && final` goes to lsqpack_huff_decode_full (lsqpack.c:
+ * 3520-3535, 3443-3517; callers 3718, 3795, 4714, 4824, 4908).  A server
+ * that batches literals over many connections holds many such partial
+ * literals; qhuff_decode_stream decodes one chunk of each of n strings per
+ * call.  QHUFF_FEATURE_STREAM and the symbols announce it (the ABI version
+ * is unchanged).
+ *
+ * Chunk i is in[in_off[i] .. in_off[i+1]), the next bytes of string i, and
+ * behaves like lsqpack_huff_decode_full(src, len, dst, dst_len, &st, final)
+ * given a dst_len that cannot run out (qdec_huff_dec4bits, lsqpack.c:
+ * 5213-5231):
+ *   state[i]   carries string i from call to call.  Zeroed: a fresh string
+ *              (the reference's resume == 0, lsqpack.c:3463-3464).  On input
+ *              only .state is read: the id of the internal node of the code
+ *              tree the string has reached -- 0 is the root, the other ids
+ *              are THIS LIBRARY'S numbering (the tree's 256 internal nodes
+ *              in the order of their bit prefixes; the reference's own
+ *              numbering lives in its huff-tables.h) and opaque to the
+ *              caller: a string begun by this call is continued by this call,
+ *              not by the reference's decoder, and the other way round.  On
+ *              output .eos = 1 iff that node accepts (the root, or an
+ *              all-ones path of at most 7 bits).
+ *   flags[i]   bit 0 (QHUFF_STREAM_FINAL): the chunk is the string's last.
+ *              flags == NULL: no chunk is.
+ *   out        every symbol whose last bit lies in the chunk, the one the
+ *              incoming state was in the middle of included.
+ *   status[i]  QHUFF_DEC_MORE  not final; state[i] updated.
+ *              QHUFF_DEC_OK    final, and the end state accepts.
+ *              QHUFF_DEC_ERROR the EOS code completed in this chunk (final
+ *                              or not), or the chunk is final and the end
+ *                              state does not accept.  The chunk contributes
+ *                              0 output bytes; state[i] as written is
+ *                              unspecified and must not be resumed.
+ *   An empty chunk: not final -- MORE, state unchanged; final -- OK or ERROR
+ *   by the incoming state.
+ * `out` must hold qhuff_decode_stream_bound(in_bytes, n) bytes: a chunk of
+ * len bytes emits at most floor(8 * len / 5) + 1 (the pending symbol may
+ * need one bit only, and the other 8 * len - 1 bits hold at most
+ * floor((8 * len - 1) / 5) codes), so floor(8 * in_bytes / 5) + n + 16
+ * (slack, as qhuff_decode_bound's).
+ *
+ * The buffer contract above applies: the call writes out[0 .. out_off[n]),
+ * out_off[0 .. n], status[0 .. n) and state[0 .. n), nothing else; for
+ * n = 0 only out_off[0].  Read slack, 32-bit offsets (QHUFF_ERANGE, the
+ * sticky device error word) and launch timing (QHUFF_KIND_DECODE) as
+ * qhuff_decode_batch.  Asynchronous on `stream`; qhuff_decode_stream_host:
+ * host pointers, synchronous.  Every chunk is decoded by one lane: there
+ * is no cooperative walk for long chunks, and 64-chunk tiles over 3 KB take
+ * the lean kernels' out-of-line path. */
+#define QHUFF_FEATURE_STREAM 1
+#define QHUFF_DEC_MORE     2    /* HUFF_DEC_END_SRC, lsqpack.c:3425        */
+#define QHUFF_STREAM_FINAL 1    /* flags[i] bit 0                          */
+
+uint64_t qhuff_decode_stream_bound(uint64_t in_bytes, uint32_t n);
+
+int qhuff_decode_stream(qhuff_ctx *ctx, const uint8_t *in,
+                        const uint32_t *in_off, uint32_t n,
+                        struct qhuff_decode_status *state,
+                        const uint8_t *flags, uint8_t *out, uint32_t *out_off,
+                        uint8_t *status, void *stream);
+
+int qhuff_decode_stream_host(qhuff_ctx *ctx, const uint8_t *in,
+                             const uint32_t *in_off, uint32_t n,
+                             struct qhuff_decode_status *state,
+                             const uint8_t *flags, uint8_t *out,
+                             uint32_t *out_off, uint8_t *status);
+
 /* ---- literal-span pre-parse + batched literal decode (SURVEY.md 8(f)
  * rank 3).  A host pass walks only the instruction framing of QPACK wire
  * data -- field sections (RFC 9204 4.5; the reference's parse_header_prefix /

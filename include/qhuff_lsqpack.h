@@ -53,6 +53,8 @@ int qhuff_lsqpack_enc_enc_str(unsigned prefix_bits, unsigned char *dst,
  *   otherwise (resumed or non-final chunks: streaming input): the registered
  *   streaming decoder (the reference's own lsqpack_huff_decode_full,
  *   lsqpack.c:3443, always exported); with none registered: ERROR.
+ *   (Many partial literals at once: qhuff_decode_stream in qhuff.h decodes
+ *   one chunk of each per call on the GPU, with its own state numbering.)
  *   An invalid string gets the reference's answer too: ERROR -- or END_DST
  *   (the same byte-boundary back-off) when dst runs out before the
  *   reference reaches the error, and the streaming decoder's result where

@@ -36,6 +36,7 @@ struct DevTables
     uint2 enc[257];                      // {code, bits}
     uint16_t sorted[257];
     uint16_t long2[kLong2Size];
+    uint32_t nodes[kNodes];              // (qhuff_decode_stream)
 };
 
 // Host copy workers for the PCIe-inclusive path: a staging memcpy of tens
@@ -477,6 +478,7 @@ qhuff_open(int device, qhuff_ctx **ctx_out)
     memcpy(dt.win, ht->win, sizeof(dt.win));
     memcpy(dt.sorted, ht->sorted, sizeof(dt.sorted));
     memcpy(dt.long2, ht->long2, sizeof(dt.long2));
+    memcpy(dt.nodes, ht->nodes, sizeof(dt.nodes));
     memset(&c->lp, 0, sizeof(c->lp));
     c->lp.n = ht->n_long;
     memcpy(c->lp.l, ht->longc, sizeof(LongLen) * ht->n_long);
@@ -1145,6 +1147,129 @@ pipe_setup(qhuff_ctx *c)
         t = 64;
     c->pool = new CopyPool(t > 1 ? t - 1 : 0);   // + the calling thread
     c->pipe_ready = true;
+    return QHUFF_OK;
+}
+
+// ---- resumable decode (qhuff_stream.hip) -----------------------------------
+
+extern "C" uint64_t
+qhuff_decode_stream_bound(uint64_t in_bytes, uint32_t n)
+{
+    // per chunk floor(8 * len / 5) + 1: the pending symbol on one bit, then
+    // 5-bit codes
+    return in_bytes * 8 / 5 + n + 16;
+}
+
+extern "C" int
+qhuff_decode_stream(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
+                    uint32_t n, struct qhuff_decode_status *state,
+                    const uint8_t *flags, uint8_t *out, uint32_t *out_off,
+                    uint8_t *status, void *stream)
+{
+    if (!c || !in_off || !out_off || (n && (!in || !out || !status || !state)))
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    const uint64_t ts = decode_tile_strings();
+    const uint64_t tiles = (n + ts - 1) / ts;
+    int rc = prepare_launch(c, tiles, st);
+    if (rc)
+        return rc;
+    StreamArgs a;
+    a.d.in = in;
+    a.d.in_off = in_off;
+    a.d.out = out;
+    a.d.out_off = out_off;
+    a.d.status = status;
+    a.d.win = c->tab->win;
+    a.d.sorted = c->tab->sorted;
+    a.d.long2 = c->tab->long2;
+    a.d.n = n;
+    a.d.c = coord(c, tiles);
+    a.d.lp = c->lp;
+    a.nodes = c->tab->nodes;
+    a.state = state;
+    a.flags = flags;
+    // (the decode kernels' resident grid: the tiles are claimed from
+    // tickets, so any grid is correct)
+    const uint64_t wpb = (uint64_t) stream_waves_per_block();
+    const uint32_t grid = grid_for(c, tiles, wpb, c->dec_grid, &a.d.c.spread);
+    hipEvent_t e0, e1;
+    const uint32_t slot = timing_slot(c, QHUFF_KIND_DECODE, &e0, &e1);
+    HIPCHK(c, launch_stream(a, grid, st, e0, e1));
+    timing_commit(c, slot, QHUFF_KIND_DECODE);
+    return finish_launch(c, st);
+}
+
+// Host pointers: one staged round trip on the context's stream.  Stage
+// layout: [in | in_off | flags | state | out_off | status | out].
+extern "C" int
+qhuff_decode_stream_host(qhuff_ctx *c, const uint8_t *in,
+                         const uint32_t *in_off, uint32_t n,
+                         struct qhuff_decode_status *state,
+                         const uint8_t *flags, uint8_t *out,
+                         uint32_t *out_off, uint8_t *status)
+{
+    if (!c || !in_off || !out_off || (n && (!in || !out || !status || !state)))
+        return QHUFF_EINVAL;
+    if (n == 0)
+    {
+        out_off[0] = 0;
+        return QHUFF_OK;
+    }
+    if (in_off[n] < in_off[0])
+        return QHUFF_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t a0 = in_off[0], in_bytes = (uint64_t) in_off[n] - a0;
+    const uint64_t bound = qhuff_decode_stream_bound(in_bytes, n);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const size_t o_off = up16(in_bytes) + 16;
+    const size_t o_fl = o_off + up16(4ull * (n + 1));
+    const size_t o_state = o_fl + up16(n);
+    const size_t o_oo = o_state + up16(2ull * n);
+    const size_t o_st = o_oo + up16(4ull * (n + 1));
+    const size_t o_out = o_st + up16(n);
+    int rc = ensure_stage(c, o_out + up16(bound));
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t sk = c->own_stream;
+    memcpy(H, in + a0, in_bytes);
+    memcpy(H + o_off, in_off, 4ull * (n + 1));
+    if (flags)
+        memcpy(H + o_fl, flags, n);
+    memcpy(H + o_state, state, 2ull * n);
+    HIPCHK(c, hipMemcpyAsync(D, H, o_oo, hipMemcpyHostToDevice, sk));
+    // (the kernel reads the caller's offsets: `in` rebased by -in_off[0])
+    rc = qhuff_decode_stream(c, D - a0, (const uint32_t *) (D + o_off), n,
+                             (struct qhuff_decode_status *) (D + o_state),
+                             flags ? D + o_fl : nullptr, D + o_out,
+                             (uint32_t *) (D + o_oo), D + o_st, sk);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(H + o_state, D + o_state, o_out - o_state,
+                             hipMemcpyDeviceToHost, sk));
+    HIPCHK(c, hipStreamSynchronize(sk));
+    rc = mirror_error(c);
+    if (rc)
+        return rc;
+    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
+    if (total)
+    {
+        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
+                                 hipMemcpyDeviceToHost, sk));
+        HIPCHK(c, hipStreamSynchronize(sk));
+        memcpy(out, H + o_out, total);
+    }
+    memcpy(state, H + o_state, 2ull * n);
+    memcpy(out_off, H + o_oo, 4ull * (n + 1));
+    memcpy(status, H + o_st, n);
     return QHUFF_OK;
 }
 

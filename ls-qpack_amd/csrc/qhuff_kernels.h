@@ -44,6 +44,16 @@ struct DecArgs
     LongParams lp;
 };
 
+// resumable decode (qhuff_stream.hip): the decode arguments, the node table
+// and the per-string state carried across calls
+struct StreamArgs
+{
+    DecArgs d;
+    const uint32_t *nodes;       // kNodes sorted node keys (qhuff_tables.h)
+    ::qhuff_decode_status *state;    // n, read and written
+    const uint8_t *flags;        // n, or null: no chunk is final
+};
+
 struct HashArgs
 {
     const uint8_t *in;
@@ -155,6 +165,10 @@ hipError_t launch_encode(const EncArgs &a, uint32_t grid, hipStream_t st,
 hipError_t launch_decode(const DecArgs &a, uint32_t grid, hipStream_t st,
                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
                          bool keep = false, bool full = false);
+hipError_t launch_stream(const StreamArgs &a, uint32_t grid, hipStream_t st,
+                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t stream_occupancy(int *blocks_per_cu);
+int stream_waves_per_block();
 hipError_t launch_hash(const HashArgs &a, uint32_t max_grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t hash_occupancy(int *blocks_per_cu);

@@ -1,0 +1,112 @@
+// qhuff_stream.hip -- batch resumable Huffman decode kernel (gfx950).
+//
+// Reference path: the second decoder, lsqpack_huff_decode_full
+// (lsqpack.c:3443-3517, qdec_huff_dec4bits 5213-5231), which every call of
+// lsqpack_huff_decode takes that is not `resume == 0 && final`
+// (lsqpack.c:3520-3535): a literal that straddles two stream reads.
+//
+// The batch kernel's tile pipeline (qhuff_decode.hip) over another policy:
+// string i's chunk i is decoded by one lane from the tree node its earlier
+// chunks ended on (state[i].state, a node id: qhuff_tables.h) to the node it
+// ends on.  The reference walks its tree a nibble at a time; here the node
+// is turned back into its bit prefix, the one code it is in the middle of is
+// resolved with the batch kernel's tables, and the rest of the chunk takes
+// the batch kernel's window-table walk, which stops -- instead of rejecting
+// -- where a code runs past the chunk's end (qhuff_stream_impl.h).  The
+// lean structure: tiles past the 3 KB stages are coded out of line, each
+// chunk by its lane.
+#include "qhuff_stream_impl.h"
+
+#include <hip/hip_ext.h>
+
+#ifndef QH_DEC_PER
+#define QH_DEC_PER 2
+#endif
+
+namespace qhuff {
+
+__global__ __launch_bounds__(64 * kWaves) void
+qhuff_stream_kernel(StreamArgs s)
+{
+    __shared__ StreamSmem smem;
+    QH_LDS StreamSmem *sm = (QH_LDS StreamSmem *) &smem;
+    const DecArgs &a = s.d;
+    const int tid = threadIdx.x;
+    Tickets tk;
+    tk.init();
+    // the prologue of qhuff_decode_kernel: ticket claims, then the table
+    // loads, stored once the first offsets loads are out
+    const uint32_t cb = claim_block_issue(a.c, tk, QH_DEC_PER);
+    constexpr int kPer = (kWinSize / 4 + 64 * kWaves - 1) / (64 * kWaves);
+    const QH_GLB u32x4 *gw = (const QH_GLB u32x4 *) glb(a.win);
+    u32x4 v[kPer];
+#pragma unroll
+    for (int r = 0; r < kPer; ++r)
+    {
+        const int i = tid + r * 64 * kWaves;
+        v[r] = gw[i < kWinSize / 4 ? i : 0];
+    }
+    const uint16_t so = glb(a.sorted)[tid < 257 ? tid : 0];
+    static_assert(kLong2Size <= 64 * kWaves, "one long2 entry per thread");
+    static_assert(kNodes <= 64 * kWaves, "one node per thread");
+    const uint16_t l2 = glb(a.long2)[tid < kLong2Size ? tid : 0];
+    const uint32_t nd = glb(s.nodes)[tid < kNodes ? tid : 0];
+    claim_block_store(a.c, cb, &sm->tk, QH_DEC_PER);
+    clear_next_launch(a.c);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    StreamPolicy pol{a.in, sm,
+                     &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)],
+                     StreamIo{s.state, s.flags}, 0, StreamEnd{0, 0, 0}};
+    uint32_t t0, k1, k2;
+    wave_tickets(a.c, tk, &sm->tk, &t0, &k1, &k2);
+    auto tables = [&]() {
+        QH_LDS u32x4 *sw = (QH_LDS u32x4 *) sm->win;
+#pragma unroll
+        for (int r = 0; r < kPer; ++r)
+        {
+            const int i = tid + r * 64 * kWaves;
+            if (i < kWinSize / 4)
+                sw[i] = v[r];
+        }
+        if (tid < 257)
+            sm->sorted[tid] = so;
+        if (tid < kLong2Size)
+            sm->long2[tid] = l2;
+        if (tid < kNodes)
+            sm->nodes[tid] = nd;
+        if (tid == 0)
+            sm->win[kHoldIdx] = kHoldEntry;
+        __syncthreads();             // the tables
+    };
+    tile_pipeline(pol, a.c, tk, t0, k1, k2, a.in, a.in_off,
+                  a.n, a.out, a.out_off, a.status, tables);
+}
+
+hipError_t
+launch_stream(const StreamArgs &a, uint32_t grid, hipStream_t st,
+              hipEvent_t ev0, hipEvent_t ev1)
+{
+    if (ev0)
+        hipExtLaunchKernelGGL(qhuff_stream_kernel, dim3(grid),
+                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
+    else
+        hipLaunchKernelGGL(qhuff_stream_kernel, dim3(grid), dim3(64 * kWaves),
+                           0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t
+stream_occupancy(int *blocks_per_cu)
+{
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        blocks_per_cu, reinterpret_cast<const void *>(qhuff_stream_kernel),
+        64 * kWaves, 0);
+}
+
+int
+stream_waves_per_block()
+{
+    return kWaves;
+}
+
+}  // namespace qhuff

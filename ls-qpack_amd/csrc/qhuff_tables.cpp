@@ -5,6 +5,8 @@
 
 #include <string.h>
 
+#include <set>
+
 namespace qhuff {
 
 namespace {
@@ -106,6 +108,22 @@ build_tables(HostTables *t)
                 ? (uint16_t) ((uint32_t) sym | ((uint32_t) (L - 14) << 9))
                 : (uint16_t) 0xffff;
         }
+
+    // internal nodes: every proper prefix of every code, once
+    {
+        std::set<uint32_t> keys;
+        for (int s = 0; s < 257; ++s)
+            for (int d = 0; d < kLen[s]; ++d)
+            {
+                const uint32_t p = d ? t->code[s] >> (kLen[s] - d) : 0u;
+                keys.insert((((p << 1) | 1u) << (31 - d)) ^ kNodeRoot);
+            }
+        memset(t->nodes, 0xff, sizeof(t->nodes));
+        int i = 0;
+        for (uint32_t k : keys)
+            if (i < kNodes)
+                t->nodes[i++] = k;
+    }
 
     t->n_long = 0;
     for (int L = kWinBits + 1; L <= 30; ++L)

@@ -16,6 +16,9 @@
 //                 nibble FSM there, lsqpack.c:5452-5465)
 //   sorted[257]   symbols in canonical order (index -> symbol)
 //   long2[640]    long codes by leading ones + 5 bits (decoder long step)
+//   nodes[256]    the code tree's internal nodes, as sorted bit prefixes --
+//                 the resumable decoder's state between chunks
+//                 (qhuff_stream_impl.h)
 #pragma once
 #include <stdint.h>
 
@@ -91,6 +94,14 @@ constexpr int kLong2N1 = 12;
 constexpr int kLong2Rows = 32 - kLong2N1;
 constexpr int kLong2Size = kLong2Rows * 32;
 
+// The code tree has 257 leaves and so 256 internal nodes: the proper
+// prefixes of the codes.  A node of depth d (<= 29) with prefix bits p is the
+// key (p << 1 | 1) << (31 - d): the prefix left-aligned, then a marker one.
+// nodes[id] = key ^ 0x80000000, ascending; the root (no bits, key
+// 0x80000000) is id 0, and a key is found again by binary search.
+constexpr int kNodes = 256;
+constexpr uint32_t kNodeRoot = 0x80000000u;
+
 struct HostTables
 {
     uint32_t code[257];
@@ -100,6 +111,7 @@ struct HostTables
     uint32_t n_long;
     uint16_t sorted[257];
     uint16_t long2[kLong2Size];
+    uint32_t nodes[kNodes];
 };
 
 void build_tables(HostTables *t);

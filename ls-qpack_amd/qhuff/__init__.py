@@ -19,6 +19,8 @@ OK = 0
 EINVAL, ENOMEM, ENODEV, ERANGE, EDEVICE = -22, -12, -19, -34, -5
 ENC_PAYLOAD, ENC_LITERAL3, ENC_LITERAL5, ENC_LITERAL7 = 0, 3, 5, 7
 DEC_OK, DEC_ERROR = 0, 1
+DEC_MORE = 2                              # QHUFF_DEC_MORE (qhuff_decode_stream)
+STREAM_FINAL = 1                          # QHUFF_STREAM_FINAL, flags bit 0
 HUFF_DEC_OK, HUFF_DEC_END_SRC, HUFF_DEC_END_DST, HUFF_DEC_ERROR = 0, 1, 2, 3
 
 # every function include/qhuff.h declares (checked by tests/test_abi.py)
@@ -40,6 +42,8 @@ EXPORTS = (
     "qhuff_dec_int", "qhuff_encode_batch_host_multi",
     "qhuff_decode_batch_host_multi", "qhuff_encode_batch_multi",
     "qhuff_decode_batch_multi", "qhuff_host_register", "qhuff_host_unregister",
+    "qhuff_decode_stream_bound", "qhuff_decode_stream",
+    "qhuff_decode_stream_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -242,6 +246,14 @@ def lib():
         L.qhuff_host_register.argtypes = [vp, C.c_size_t]
         L.qhuff_host_unregister.restype = C.c_int
         L.qhuff_host_unregister.argtypes = [vp]
+        L.qhuff_decode_stream_bound.restype = C.c_uint64
+        L.qhuff_decode_stream_bound.argtypes = [C.c_uint64, C.c_uint32]
+        L.qhuff_decode_stream.restype = C.c_int
+        L.qhuff_decode_stream.argtypes = [vp, vp, u32p, C.c_uint32, vp, vp,
+                                          vp, u32p, vp, vp]
+        L.qhuff_decode_stream_host.restype = C.c_int
+        L.qhuff_decode_stream_host.argtypes = [vp, vp, u32p, C.c_uint32, vp,
+                                               vp, vp, u32p, vp]
         _lib = L
     return _lib
 
@@ -254,6 +266,10 @@ def encode_bound(in_bytes, n, mode=ENC_PAYLOAD):
 
 def decode_bound(in_bytes, n):
     return int(lib().qhuff_decode_bound(in_bytes, n))
+
+
+def decode_stream_bound(in_bytes, n):
+    return int(lib().qhuff_decode_stream_bound(in_bytes, n))
 
 
 def _np_ptr(a):
@@ -601,6 +617,57 @@ class Codec:
         status = torch.empty(max(n, 1), dtype=torch.uint8, device=data.device)
         self.decode_into(data, in_off, n, out, out_off, status, stream)
         return out, out_off, status[:n]
+
+    # resumable decode: one chunk of each string per call ---------------------
+    def decode_stream_into(self, data, in_off, n, state, flags, out, out_off,
+                           status, stream=None):
+        """qhuff_decode_stream: state is a uint8 tensor [n, 2] ({state, eos}
+        per string, read and written), flags a uint8 tensor [n] or None."""
+        rc = lib().qhuff_decode_stream(
+            self._ctx, data.data_ptr(), in_off.data_ptr(), n,
+            state.data_ptr(), flags.data_ptr() if flags is not None else None,
+            out.data_ptr(), out_off.data_ptr(), status.data_ptr(),
+            self._stream(stream))
+        self._check(rc, "qhuff_decode_stream")
+
+    def decode_stream(self, data, in_off, state=None, flags=None, stream=None):
+        """One chunk of each of n strings (device tensors).  state None: fresh
+        strings.  Returns (out, out_off, status, state): state is updated in
+        place and passed to the call that continues the strings."""
+        import torch
+        n = in_off.numel() - 1
+        if state is None:
+            state = torch.zeros((max(n, 1), 2), dtype=torch.uint8,
+                                device=data.device)
+        out = torch.empty(decode_stream_bound(int(data.numel()), n),
+                          dtype=torch.uint8, device=data.device)
+        out_off = torch.empty(n + 1, dtype=torch.int32, device=data.device)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=data.device)
+        self.decode_stream_into(data, in_off, n, state, flags, out, out_off,
+                                status, stream)
+        return out, out_off, status[:n], state
+
+    def decode_stream_host(self, data, in_off, state=None, flags=None):
+        """qhuff_decode_stream_host over numpy arrays -> (out, out_off,
+        status, state); state: uint8 [n, 2], a copy updated by the call."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint32)
+        n = len(in_off) - 1
+        state = (np.zeros((max(n, 1), 2), dtype=np.uint8) if state is None
+                 else np.array(state, dtype=np.uint8).reshape(-1, 2))
+        if flags is not None:
+            flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        out = np.zeros(decode_stream_bound(int(in_off[-1] - in_off[0]), n),
+                       dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint32)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = lib().qhuff_decode_stream_host(
+            self._ctx, _np_ptr(data), _np_ptr(in_off), n, _np_ptr(state),
+            _np_ptr(flags) if flags is not None else None, _np_ptr(out),
+            _np_ptr(out_off), _np_ptr(status))
+        self._check(rc, "qhuff_decode_stream_host")
+        return out[:out_off[-1]], out_off, status[:n], state[:n]
 
     # header hashing (XXH32, lsqpack.c:1681-1685) ---------------------------
     def xxh32_headers_into(self, data, off, n, seed, name_hash, nameval_hash,
