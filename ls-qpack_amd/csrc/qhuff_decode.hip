@@ -52,19 +52,8 @@ qhuff_decode_kernel(DecArgs a)
     // then are the tables stored and the second barrier passed (in
     // tile_pipeline's mid()): the offsets loads overlap the table loads.
     const uint32_t cb = claim_block_issue(a.c, tk, QH_DEC_PER);
-    constexpr int kPer = (kWinSize / 4 + 64 * kWaves - 1) / (64 * kWaves);
-    const QH_GLB u32x4 *gw = (const QH_GLB u32x4 *) glb(a.win);
-    u32x4 v[kPer];
-#pragma unroll
-    for (int r = 0; r < kPer; ++r)
-    {
-        const int i = tid + r * 64 * kWaves;
-        v[r] = gw[i < kWinSize / 4 ? i : 0];
-    }
-    const QH_GLB uint16_t *gs = glb(a.sorted);
-    const uint16_t so = gs[tid < 257 ? tid : 0];
-    static_assert(kLong2Size <= 64 * kWaves, "one long2 entry per thread");
-    const uint16_t l2 = glb(a.long2)[tid < kLong2Size ? tid : 0];
+    DecTableLoads tl;
+    tl.issue(a.win, a.sorted, a.long2, tid);
     claim_block_store(a.c, cb, &sm->tk, QH_DEC_PER);
     clear_next_launch(a.c);
     // the tickets: LDS stores visible, no wait for the table loads (a
@@ -78,21 +67,10 @@ qhuff_decode_kernel(DecArgs a)
 #endif
     uint32_t t0, k1, k2;
     wave_tickets(a.c, tk, &sm->tk, &t0, &k1, &k2);
-    auto tables = [&]() {
-        QH_LDS u32x4 *sw = (QH_LDS u32x4 *) sm->win;
-#pragma unroll
-        for (int r = 0; r < kPer; ++r)
-        {
-            const int i = tid + r * 64 * kWaves;
-            if (i < kWinSize / 4)
-                sw[i] = v[r];
-        }
-        if (tid < 257)
-            sm->sorted[tid] = so;
-        if (tid < kLong2Size)
-            sm->long2[tid] = l2;
-        if (tid == 0)
-            sm->win[kHoldIdx] = kHoldEntry;
+    // (tl by value: by reference the kernel's prologue is scheduled
+    // differently)
+    auto tables = [&, tl]() {
+        tl.store(sm, tid);
         __syncthreads();             // the tables
     };
     tile_pipeline(pol, a.c, tk, t0, k1, k2, a.in, a.in_off,

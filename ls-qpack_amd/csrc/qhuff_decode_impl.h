@@ -1,6 +1,8 @@
 // qhuff_decode_impl.h -- the decode side of the kernels: window-table
 // step loop, arena compaction, slow tiles and the tile policy, shared by the
-// batch kernel (qhuff_decode.hip) and the service kernel (qhuff_service.hip).
+// batch kernel (qhuff_decode.hip) and the service kernel (qhuff_service.hip);
+// the resumable decoder (qhuff_stream_impl.h) builds on the step loop, the
+// sources, the emitters and the table staging.
 // See qhuff_decode.hip for the algorithm.
 #pragma once
 
@@ -73,6 +75,51 @@ struct DecSmem
     uint16_t long2[kLong2Size];      // long codes by leading ones
     DecWave w[kWaves];
     BlockTickets tk;                 // the workgroup's first tickets
+};
+
+// The decode tables on their way into a workgroup's DecSmem: issue() starts
+// this thread's global loads of win, sorted and long2 and holds them in
+// registers; store() puts them, with the hold entry, into LDS.  A kernel
+// issues in its prologue and stores inside the tables() step of
+// tile_pipeline, so the first offsets loads overlap the table loads
+// (qhuff_decode.hip); the barrier after the stores is the caller's.
+struct DecTableLoads
+{
+    static constexpr int kPer = (kWinSize / 4 + 64 * kWaves - 1) / (64 * kWaves);
+    static_assert(kLong2Size <= 64 * kWaves, "one long2 entry per thread");
+    u32x4 v[kPer];
+    uint16_t so, l2;
+    __device__ __forceinline__ void issue(const uint32_t *win,
+                                          const uint16_t *sorted,
+                                          const uint16_t *long2, int tid)
+    {
+        const QH_GLB u32x4 *gw = (const QH_GLB u32x4 *) glb(win);
+#pragma unroll
+        for (int r = 0; r < kPer; ++r)
+        {
+            const int i = tid + r * 64 * kWaves;
+            v[r] = gw[i < kWinSize / 4 ? i : 0];
+        }
+        so = glb(sorted)[tid < 257 ? tid : 0];
+        l2 = glb(long2)[tid < kLong2Size ? tid : 0];
+    }
+    __device__ __forceinline__ void store(QH_LDS DecSmem *sm, int tid) const
+    {
+        QH_LDS u32x4 *sw = (QH_LDS u32x4 *) sm->win;
+#pragma unroll
+        for (int r = 0; r < kPer; ++r)
+        {
+            const int i = tid + r * 64 * kWaves;
+            if (i < kWinSize / 4)
+                sw[i] = v[r];
+        }
+        if (tid < 257)
+            sm->sorted[tid] = so;
+        if (tid < kLong2Size)
+            sm->long2[tid] = l2;
+        if (tid == 0)
+            sm->win[kHoldIdx] = kHoldEntry;
+    }
 };
 
 struct DecLds                        // big-endian dwords staged in LDS
@@ -261,8 +308,10 @@ decode_string(const Src &src, uint32_t bit0, uint32_t bitend,
     return bad ? -1 - (int) emit.n : (int) emit.n;
 }
 
-// Lean variant used by the staged (LDS) path (same return value).  The bit stream sits in two
-// dwords A:B with a position t: the 32-bit window is alignbit(A, B, t) --
+// Lean variant used by the staged (LDS) path (same return value), in two
+// parts: window_walk(), the main phase, and tail_lookup(), the last
+// < kWinBits bits; the resumable decoder (qhuff_stream_impl.h) is built from
+// the same two.  The bit stream sits in two dwords A:B with a position t: the 32-bit window is alignbit(A, B, t) --
 // ((A:B) >> t), the next bit at A's bit 31 - (32 - t) -- valid for t in
 // [0, 31] (t = 0: the window is B).  Consuming c bits lowers t; when it goes
 // negative the window moves on a dword (A = B, B = the next dword, read one
@@ -278,22 +327,46 @@ decode_string(const Src &src, uint32_t bit0, uint32_t bitend,
 // R2: two main steps per loop trip share one refill read of the next input
 // dword (step lab at 12 waves/CU: 8,633 vs 9,795 cycles per tile; decode
 // 62.7 vs 64.0 us in-process, profiles/r03_p); false: one read per step.
-template <class Emit, bool R2 = true>
-__device__ __forceinline__ int
-decode_string_lds(const QH_LDS uint32_t *src, uint32_t bit0, uint32_t bitend,
-                  const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_sorted,
-                  const QH_LDS uint16_t *s_long2, Emit &emit)
+
+// Stop policy of the walk: what a long code that runs past the end of the
+// bits does to its lane.  past_end(past, W, rem) is told whether this lane
+// sits on such a code (the window W, rem < its length real bits left) and
+// returns whether the lane stops there, its rem zeroed, without an error.
+// A whole string's bits hold no such code: the lane is rejected (D3).
+struct RejectPastEnd
 {
-    uint32_t rem = bitend - bit0;            // real bits not yet consumed
+    __device__ __forceinline__ bool past_end(bool, uint32_t, uint32_t) const
+    {
+        return false;
+    }
+};
+
+struct Walked                        // where window_walk() left its lane
+{
+    uint32_t W;                      // the window at the first bit not consumed
+    uint32_t rem;                    // real bits not consumed: < kWinBits
+    uint32_t bad;                    // rejected (then rem = 0)
+};
+
+// The main phase over the bits [bit0, bit0 + rem) of the big-endian dword
+// stream `src` (src.dw(i), readable two dwords past the last bit).  State by
+// value, result by value: references to rem and bad cost the batch kernel
+// its operand order and a v_mov.
+template <bool R2, class Src, class Emit, class Stop>
+__device__ __forceinline__ Walked
+window_walk(const Src &src, uint32_t bit0, uint32_t rem,
+            const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_long2,
+            Emit &emit, Stop &stop)
+{
     uint32_t A, B, t, p, nx;
     {
         const uint32_t i0 = bit0 >> 5, sk = bit0 & 31;
-        A = src[i0];
-        const uint32_t a1 = src[i0 + 1];
+        A = src.dw(i0);
+        const uint32_t a1 = src.dw(i0 + 1);
         B = sk ? a1 : A;                     // sk == 0: the window is B = A
         t = (32 - sk) & 31;
         p = sk ? i0 + 2 : i0 + 1;
-        nx = src[p];
+        nx = src.dw(p);
     }
     uint32_t bad = 0;                        // (a u32: no lane-mask phis)
     // No lane branches in the step: a lane with < kWinBits real bits left
@@ -338,7 +411,7 @@ decode_string_lds(const QH_LDS uint32_t *src, uint32_t bit0, uint32_t bitend,
         rem -= c;
         advance(c);
         if constexpr (!R2)
-            nx = src[p];
+            nx = src.dw(p);
         W = __builtin_amdgcn_alignbit(A, B, t);
         idx = win_addr(W, rem >= kMain);
         if constexpr (R2)
@@ -354,12 +427,13 @@ decode_string_lds(const QH_LDS uint32_t *src, uint32_t bit0, uint32_t bitend,
             emit(e, ent_ns(e));
             rem -= c2;
             advance(c2);
-            nx = src[p];
+            nx = src.dw(p);
             W = __builtin_amdgcn_alignbit(A, B, t);
             idx = win_addr(W, rem >= kMain);
         }
         // lanes with >= kMain bits on a marker sit on a code of 14..30
-        // bits; EOS, or a code running past the end, rejects the string (D3)
+        // bits; EOS rejects the string, and so does a code running past the
+        // end (D3) unless the stop policy takes the lane
         const bool lng = (rem >= kMain) & (e < (1u << 24));
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(lng) != 0, 0))
         {
@@ -370,37 +444,65 @@ decode_string_lds(const QH_LDS uint32_t *src, uint32_t bit0, uint32_t bitend,
             const uint32_t x = (W << ((n1 + 1) & 31)) >> 27;
             const uint32_t l2 = s_long2[(lng ? n1 - kLong2N1 : 0u) * 32 + x];
             const uint32_t sym = l2 & 511, L = (l2 >> 9) + 14;
-            const bool rej = lng & ((sym == 256) | (L > rem));
-            const bool ok = lng & !rej;
+            const bool halt = stop.past_end(lng & (L > rem), W, rem);
+            const bool rej = lng & !halt & ((sym == 256) | (L > rem));
+            const bool ok = lng & !halt & !rej;
             const uint32_t cl = ok ? L : 0u;
             emit(sym, ok ? 1u : 0u);
             bad |= rej ? 1u : 0u;
-            rem = rej ? 0u : rem - cl;
+            rem = (rej | halt) ? 0u : rem - cl;
             advance(cl);
-            nx = src[p];
+            nx = src.dw(p);
             W = __builtin_amdgcn_alignbit(A, B, t);
             idx = win_addr(W, rem >= kMain);
         }
     } while (__builtin_amdgcn_ballot_w64(rem >= kMain));
+    return Walked{W, rem, bad};
+}
 
-    // epilogue, one pass: the last < kWinBits (13) real bits hold at most
-    // two symbols (codes are >= 5 bits), both inside the window padded with
-    // ones, so one lookup decodes them; the bits after them cannot complete
-    // a code (its entry would have decoded it), so they are the padding, and
-    // the D3 tail rule (fewer than 8 bits, all ones) applies at once.  The
-    // EOS code (30 bits) cannot occur in 12 bits.
+// The last < kWinBits (13) real bits, one pass: they hold at most
+// two symbols (codes are >= 5 bits), both inside the window padded with
+// ones, so one lookup decodes them; the bits after them cannot complete
+// a code (its entry would have decoded it).  The EOS code (30 bits) cannot
+// occur in 12 bits.  Returns the padded window w, the bits c of the symbols
+// emitted (live lanes emit) and the r2 = rem - c bits behind them.
+struct Tail
+{
+    uint32_t w, c, r2;
+};
+template <class Emit>
+__device__ __forceinline__ Tail
+tail_lookup(uint32_t W, uint32_t rem, bool live, const QH_LDS uint32_t *s_win,
+            Emit &emit)
+{
+    const uint32_t w = W | (0xffffffffu >> (rem & 31));
+    const uint32_t e = s_win[w >> (32 - kWinBits)];
+    const uint32_t ns = ent_ns(e), ct = ent_c(e), l0 = ent_l0(e);
+    const bool two = (ns == 2) & (ct <= rem);
+    const bool one = !two & (ns != 0) & (l0 <= rem);
+    const uint32_t c = two ? ct : (one ? l0 : 0u);
+    emit(e, live ? (two ? 2u : (one ? 1u : 0u)) : 0u);
+    return Tail{w, c, rem - c};
+}
+
+template <class Emit, bool R2 = true>
+__device__ __forceinline__ int
+decode_string_lds(const QH_LDS uint32_t *src, uint32_t bit0, uint32_t bitend,
+                  const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_sorted,
+                  const QH_LDS uint16_t *s_long2, Emit &emit)
+{
+    RejectPastEnd stop;
+    const Walked k = window_walk<R2>(DecLds{src}, bit0, bitend - bit0, s_win,
+                                     s_long2, emit, stop);
+    uint32_t bad = k.bad;
+    // epilogue: the r2 bits behind the last symbols are the padding, and the
+    // D3 tail rule (fewer than 8 bits, all ones) applies at once
     {
-        const bool live = !(bad || rem == 0);
-        const uint32_t w = W | (0xffffffffu >> (rem & 31));
-        const uint32_t e = s_win[w >> (32 - kWinBits)];
-        const uint32_t ns = ent_ns(e), ct = ent_c(e), l0 = ent_l0(e);
-        const bool two = (ns == 2) & (ct <= rem);
-        const bool one = !two & (ns != 0) & (l0 <= rem);
-        const uint32_t c = two ? ct : (one ? l0 : 0u);
-        emit(e, live ? (two ? 2u : (one ? 1u : 0u)) : 0u);
-        const uint32_t r2 = rem - c;             // padding bits
-        const uint32_t inv = ~(w << (c & 31));   // padding bits at the top
-        const bool pad_ok = r2 < 8 && (r2 == 0 || (inv >> ((32 - r2) & 31)) == 0);
+        const bool live = !(bad || k.rem == 0);
+        const Tail tl = tail_lookup(k.W, k.rem, live, s_win, emit);
+        const uint32_t inv = ~(tl.w << (tl.c & 31));   // padding bits at the top
+        const bool pad_ok = tl.r2 < 8
+                         && (tl.r2 == 0 || (inv >> ((32 - tl.r2) & 31)) == 0);
         bad |= (live & !pad_ok) ? 1u : 0u;
     }
     emit.finish();
@@ -428,6 +530,7 @@ struct ArenaEmit
 struct CountEmit
 {
     uint32_t n;
+    __device__ __forceinline__ void finish() {}
     __device__ __forceinline__ void operator()(uint32_t, uint32_t nb)
     {
         n += nb;
@@ -438,6 +541,7 @@ struct GlobalEmit                            // slow path: byte stores
 {
     uint8_t *dst;
     uint32_t n;
+    __device__ __forceinline__ void finish() {}
     __device__ __forceinline__ void operator()(uint32_t val, uint32_t nb)
     {
         if (nb >= 1)
@@ -932,7 +1036,6 @@ compact_wave(const QH_LDS uint8_t *src, QH_LDS uint8_t *dstb, uint32_t n)
     write_bytes(dstb, vh, h);
     write_bytes(dstb + it, vt, nt);
 }
-
 
 
 // A tile whose input or output does not fit the stage, coded eagerly:

@@ -11,10 +11,12 @@
 // ends on.  The reference walks its tree a nibble at a time; here the node
 // is turned back into its bit prefix, the one code it is in the middle of is
 // resolved with the batch kernel's tables, and the rest of the chunk takes
-// the batch kernel's window-table walk, which stops -- instead of rejecting
-// -- where a code runs past the chunk's end (qhuff_stream_impl.h).  The
-// lean structure: tiles past the 3 KB stages are coded out of line, each
-// chunk by its lane.
+// the batch kernel's window-table walk itself (window_walk,
+// qhuff_decode_impl.h) under a stop policy that stops -- instead of
+// rejecting -- where a code runs past the chunk's end
+// (qhuff_stream_impl.h).  The tables' staging, the LDS layout, the staged
+// source and the emitters are the batch kernel's too.  The lean structure:
+// tiles past the 3 KB stages are coded out of line, each chunk by its lane.
 #include "qhuff_stream_impl.h"
 
 #include <hip/hip_ext.h>
@@ -37,19 +39,9 @@ qhuff_stream_kernel(StreamArgs s)
     // the prologue of qhuff_decode_kernel: ticket claims, then the table
     // loads, stored once the first offsets loads are out
     const uint32_t cb = claim_block_issue(a.c, tk, QH_DEC_PER);
-    constexpr int kPer = (kWinSize / 4 + 64 * kWaves - 1) / (64 * kWaves);
-    const QH_GLB u32x4 *gw = (const QH_GLB u32x4 *) glb(a.win);
-    u32x4 v[kPer];
-#pragma unroll
-    for (int r = 0; r < kPer; ++r)
-    {
-        const int i = tid + r * 64 * kWaves;
-        v[r] = gw[i < kWinSize / 4 ? i : 0];
-    }
-    const uint16_t so = glb(a.sorted)[tid < 257 ? tid : 0];
-    static_assert(kLong2Size <= 64 * kWaves, "one long2 entry per thread");
+    DecTableLoads tl;
+    tl.issue(a.win, a.sorted, a.long2, tid);
     static_assert(kNodes <= 64 * kWaves, "one node per thread");
-    const uint16_t l2 = glb(a.long2)[tid < kLong2Size ? tid : 0];
     const uint32_t nd = glb(s.nodes)[tid < kNodes ? tid : 0];
     claim_block_store(a.c, cb, &sm->tk, QH_DEC_PER);
     clear_next_launch(a.c);
@@ -59,23 +51,10 @@ qhuff_stream_kernel(StreamArgs s)
                      StreamIo{s.state, s.flags}, 0, StreamEnd{0, 0, 0}};
     uint32_t t0, k1, k2;
     wave_tickets(a.c, tk, &sm->tk, &t0, &k1, &k2);
-    auto tables = [&]() {
-        QH_LDS u32x4 *sw = (QH_LDS u32x4 *) sm->win;
-#pragma unroll
-        for (int r = 0; r < kPer; ++r)
-        {
-            const int i = tid + r * 64 * kWaves;
-            if (i < kWinSize / 4)
-                sw[i] = v[r];
-        }
-        if (tid < 257)
-            sm->sorted[tid] = so;
-        if (tid < kLong2Size)
-            sm->long2[tid] = l2;
+    auto tables = [&, tl]() {
+        tl.store(sm, tid);
         if (tid < kNodes)
             sm->nodes[tid] = nd;
-        if (tid == 0)
-            sm->win[kHoldIdx] = kHoldEntry;
         __syncthreads();             // the tables
     };
     tile_pipeline(pol, a.c, tk, t0, k1, k2, a.in, a.in_off,

@@ -1,6 +1,8 @@
 // qhuff_stream_impl.h -- the resumable decoder: a chunk of a string, from
 // the tree node the string's earlier chunks ended on to the node this one
 // ends on (qhuff_decode_stream, include/qhuff.h).  See qhuff_stream.hip.
+// Here: the nodes, the pending-code start, the stop policy and the tile
+// policy; the step loop and the tail lookup are qhuff_decode_impl.h's.
 #pragma once
 
 #include "qhuff_decode_impl.h"
@@ -44,14 +46,9 @@ node_find(const QH_LDS uint32_t *s_nodes, uint32_t key)
     return lo;
 }
 
-struct StreamLds                     // big-endian dwords staged in LDS
-{
-    const QH_LDS uint32_t *w;
-    uint32_t bitend;
-    // (the stage has slack past the input: reading ahead is always safe)
-    __device__ __forceinline__ uint32_t dw(uint32_t i) const { return w[i]; }
-};
-struct StreamGlb                     // raw little-endian bytes in global
+// The chunk's source past the stage: raw little-endian bytes in global
+// (staged chunks read DecLds)
+struct StreamGlb
 {
     const QH_GLB uint32_t *w;
     uint32_t bitend;
@@ -62,18 +59,20 @@ struct StreamGlb                     // raw little-endian bytes in global
     }
 };
 
-struct StreamCount                   // slow path: sizes only
+// Stop policy of window_walk(): a long code running past the chunk's end
+// stops its lane there.  The chunk's bits complete no code (the table would
+// have found it, whatever lies behind them): the rem <= 29 left are the
+// node reached.  held: `key` is set, the rest of the chunk is skipped.
+struct StopAtNode
 {
-    uint32_t n;
-    __device__ __forceinline__ void finish() {}
-    __device__ __forceinline__ void operator()(uint32_t, uint32_t nb)
+    uint32_t key, held;
+    __device__ __forceinline__ bool past_end(bool past, uint32_t W,
+                                             uint32_t rem)
     {
-        n += nb;
+        key = past ? node_key(W, rem) : key;
+        held |= past ? 1u : 0u;
+        return past;
     }
-};
-struct StreamStore : GlobalEmit      // slow path: byte stores
-{
-    __device__ __forceinline__ void finish() {}
 };
 
 struct StreamEnd
@@ -92,23 +91,24 @@ struct StreamEnd
 //          window table or the canonical search, it is emitted and the walk
 //          starts behind it; a chunk that ends before the code does descends
 //          the node by all its bits and emits nothing;
-//   walk   decode_string_lds()'s step loop, except that a long code running
-//          past the chunk's end stops the lane there (in decode_string_lds it
-//          rejects the string); the EOS code rejects as before;
+//   walk   window_walk(), the batch decoder's step loop
+//          (qhuff_decode_impl.h), under the StopAtNode policy: a long code
+//          running past the chunk's end stops the lane there (in
+//          decode_string_lds it rejects the string); the EOS code rejects
+//          as before;
 //   end    the bits behind the last complete symbol (<= 29: no code is
 //          complete) are the node reached; a final chunk is accepted iff
 //          that node accepts -- the D3 tail rule over the carried bits too.
 template <class Src, class Emit>
 __device__ __forceinline__ StreamEnd
-stream_decode(const Src &src, uint32_t bit0, uint32_t node_in, bool fin,
-              const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_sorted,
-              const QH_LDS uint16_t *s_long2, const QH_LDS uint32_t *s_nodes,
-              Emit &emit)
+stream_decode(const Src &src, uint32_t bit0, uint32_t bitend, uint32_t node_in,
+              bool fin, const QH_LDS uint32_t *s_win,
+              const QH_LDS uint16_t *s_sorted, const QH_LDS uint16_t *s_long2,
+              const QH_LDS uint32_t *s_nodes, Emit &emit)
 {
-    uint32_t rem = src.bitend - bit0;        // real bits not yet consumed
+    uint32_t rem = bitend - bit0;            // real bits not yet consumed
     uint32_t bad = 0;                        // (a u32: no lane-mask phis)
-    uint32_t held = 0;                       // `key` is set: skip the rest
-    uint32_t key = kNodeRoot;                // the node reached
+    StopAtNode stop{kNodeRoot, 0};           // the node reached
     const uint32_t kin = s_nodes[node_in & (kNodes - 1)] ^ kNodeRoot;
     const uint32_t d = node_depth(kin);
     if (__builtin_amdgcn_ballot_w64(d != 0))
@@ -136,99 +136,20 @@ stream_decode(const Src &src, uint32_t bit0, uint32_t node_in, bool fin,
         const bool stay = pend & !done;      // then d + rem <= 29
         emit(sym, (done & !eosc) ? 1u : 0u);
         bad |= eosc ? 1u : 0u;
-        key = stay ? node_key(W, d + rem) : key;
-        held |= (stay | eosc) ? 1u : 0u;
+        stop.key = stay ? node_key(W, d + rem) : stop.key;
+        stop.held |= (stay | eosc) ? 1u : 0u;
         const uint32_t c = done ? need : 0u;
         bit0 += c;
         rem = (stay | eosc) ? 0u : rem - c;
     }
 
-    // the walk: decode_string_lds() (qhuff_decode_impl.h), which documents
-    // the step
-    uint32_t A, B, t, p, nx;
-    {
-        const uint32_t i0 = bit0 >> 5, sk = bit0 & 31;
-        A = src.dw(i0);
-        const uint32_t a1 = src.dw(i0 + 1);
-        B = sk ? a1 : A;
-        t = (32 - sk) & 31;
-        p = sk ? i0 + 2 : i0 + 1;
-        nx = src.dw(p);
-    }
-    constexpr uint32_t kMain = kWinBits;
-    uint32_t W = __builtin_amdgcn_alignbit(A, B, t);
-    auto win_addr = [](uint32_t w, bool live) -> uint32_t {
-        return ((w >> (32 - kWinBits - 2)) & (live ? 4u * (kWinSize - 1) : 0u))
-             | (live ? 0u : 4u * kHoldIdx);
-    };
-    uint32_t idx = win_addr(W, rem >= kMain);
-    auto advance = [&](uint32_t c) {
-        uint32_t tn;
-        const bool cross = __builtin_sub_overflow(t, c, &tn);
-        A = cross ? B : A;
-        B = cross ? nx : B;
-        t = tn & 31;
-        p += cross ? 1u : 0u;
-    };
-    if (__builtin_amdgcn_ballot_w64(rem >= kMain))
-    do
-    {
-        uint32_t e = *(const QH_LDS uint32_t *) ((const QH_LDS uint8_t *) s_win + idx);
-        const uint32_t c = ent_c(e);
-        emit(e, ent_ns(e));
-        rem -= c;
-        advance(c);
-        W = __builtin_amdgcn_alignbit(A, B, t);
-        idx = win_addr(W, rem >= kMain);
-        e = *(const QH_LDS uint32_t *) ((const QH_LDS uint8_t *) s_win + idx);
-        const uint32_t c2 = ent_c(e);
-        emit(e, ent_ns(e));
-        rem -= c2;
-        advance(c2);
-        nx = src.dw(p);
-        W = __builtin_amdgcn_alignbit(A, B, t);
-        idx = win_addr(W, rem >= kMain);
-        const bool lng = (rem >= kMain) & (e < (1u << 24));
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(lng) != 0, 0))
-        {
-            const uint32_t n1 = min(~W ? (uint32_t) __builtin_clz(~W) : 32u,
-                                    31u);
-            const uint32_t x = (W << ((n1 + 1) & 31)) >> 27;
-            const uint32_t l2 = s_long2[(lng ? n1 - kLong2N1 : 0u) * 32 + x];
-            const uint32_t sym = l2 & 511, L = (l2 >> 9) + 14;
-            // L > rem: the chunk's bits complete no code (the table would
-            // have found it, whatever lies behind them): rem <= 29 of them
-            // are the node reached
-            const bool over = lng & (L > rem);
-            const bool rej = lng & !over & (sym == 256);
-            const bool ok = lng & !over & !rej;
-            const uint32_t cl = ok ? L : 0u;
-            emit(sym, ok ? 1u : 0u);
-            bad |= rej ? 1u : 0u;
-            key = over ? node_key(W, rem) : key;
-            held |= over ? 1u : 0u;
-            rem = (rej | over) ? 0u : rem - cl;
-            advance(cl);
-            nx = src.dw(p);
-            W = __builtin_amdgcn_alignbit(A, B, t);
-            idx = win_addr(W, rem >= kMain);
-        }
-    } while (__builtin_amdgcn_ballot_w64(rem >= kMain));
-
-    // the last < kWinBits bits: at most two symbols in one padded lookup;
-    // the r2 (<= 12) bits behind them complete no code
-    {
-        const bool live = !(bad || rem == 0);
-        const uint32_t w = W | (0xffffffffu >> (rem & 31));
-        const uint32_t e = s_win[w >> (32 - kWinBits)];
-        const uint32_t ns = ent_ns(e), ct = ent_c(e), l0 = ent_l0(e);
-        const bool two = (ns == 2) & (ct <= rem);
-        const bool one = !two & (ns != 0) & (l0 <= rem);
-        const uint32_t c = two ? ct : (one ? l0 : 0u);
-        emit(e, live ? (two ? 2u : (one ? 1u : 0u)) : 0u);
-        const uint32_t r2 = rem - c;
-        key = held ? key : node_key(w << (c & 31), r2);
-    }
+    const Walked k = window_walk<true>(src, bit0, rem, s_win, s_long2, emit,
+                                       stop);
+    bad |= k.bad;
+    // the r2 (<= 12) bits behind the last symbols complete no code
+    const Tail tl = tail_lookup(k.W, k.rem, !(bad || k.rem == 0), s_win, emit);
+    const uint32_t key = stop.held ? stop.key
+                                   : node_key(tl.w << (tl.c & 31), tl.r2);
     emit.finish();
     StreamEnd r;
     r.eos = node_accepts(key) ? 1u : 0u;
@@ -249,14 +170,9 @@ static_assert(8 * kStreamFixMaxLen / 5 + 3 <= kFixStride, "fixed slot");
 static_assert(3 * kDecTS + 8 * kDecInCap / 5 + QH_ARENA_SLACK <= kArenaBytes,
               "slots by input offset");
 
-struct StreamSmem
+struct StreamSmem : DecSmem
 {
-    uint32_t win[kWinSize + 4];      // + the hold entry
-    uint16_t sorted[257];
-    uint16_t long2[kLong2Size];
-    uint32_t nodes[kNodes];
-    DecWave w[kWaves];
-    BlockTickets tk;
+    uint32_t nodes[kNodes];          // sorted node keys (qhuff_tables.h)
 };
 
 // a tile's offsets and its first string's index (the state and flags of
@@ -330,8 +246,8 @@ stream_slow_tile(const uint8_t *in, QH_LDS StreamSmem *sm, QH_LDS DecWave *wv,
             const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
             const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
             const StreamGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
-            StreamStore em{{dst, 0}};
-            stream_decode(src, 8 * rs, node, fin, sm->win, sm->sorted,
+            GlobalEmit em{dst, 0};
+            stream_decode(src, 8 * rs, 8 * re, node, fin, sm->win, sm->sorted,
                           sm->long2, sm->nodes, em);
         }
         if (valid)
@@ -369,9 +285,9 @@ stream_tile_sizes(const uint8_t *in, QH_LDS StreamSmem *sm, StreamIo io,
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
         const StreamGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
-        StreamCount em{0};
-        o.end = stream_decode(src, 8 * rs, node, fin, sm->win, sm->sorted,
-                              sm->long2, sm->nodes, em);
+        CountEmit em{0};
+        o.end = stream_decode(src, 8 * rs, 8 * re, node, fin, sm->win,
+                              sm->sorted, sm->long2, sm->nodes, em);
         o.st = o.end.status;
         o.sz = o.st == QHUFF_DEC_ERROR ? 0u : em.n;
     }
@@ -431,11 +347,10 @@ struct StreamPolicy
         *st = 0;
         if (valid)
         {
-            const StreamLds src{wv->in, 8 * re};
             ArenaEmit em{wv->arena + slot0, wv->arena + slot0, 0};
-            const StreamEnd e = stream_decode(src, 8 * rs, node, fin, sm->win,
-                                              sm->sorted, sm->long2,
-                                              sm->nodes, em);
+            const StreamEnd e = stream_decode(DecLds{wv->in}, 8 * rs, 8 * re,
+                                              node, fin, sm->win, sm->sorted,
+                                              sm->long2, sm->nodes, em);
             *st = e.status;
             *sz = e.status == QHUFF_DEC_ERROR ? 0u : em.n;
             io.store(to.s0, e);

@@ -238,6 +238,38 @@ def test_node_set(codec):
     assert (st[0] == qhuff.DEC_MORE).all() and (st[1] == qhuff.DEC_OK).all()
 
 
+STAGE = 3072                     # a tile's staged input bytes, at most
+
+
+@pytest.mark.gpu
+def test_node_set_past_the_stage(codec):
+    """the node set on tiles past the stage: 63 pairs to a tile of 64, the
+    64th string a long payload whose two pieces each exceed the stage, so
+    every chunk of both launches is sized and decoded from global memory
+    (stop on a code past the chunk's end, resume on a pending code)"""
+    rng = random.Random(63)
+    long_ = encoded([bytes(rng.choice(qhuff.TOKEN_ALPHABET)
+                           for _ in range(11000))])[0]
+    assert len(long_) >= 3100
+    room = len(long_) - 2 * (STAGE + 1)
+    assert room >= 255
+    nodes = node_set_pairs()
+    pairs = []
+    for t, i in enumerate(range(0, len(nodes), 63)):
+        cut = STAGE + 1 + (37 * t) % (room + 1)
+        pairs += nodes[i:i + 63] + [(long_[:cut], long_[cut:])]
+    tiles = -(-len(pairs) // 64)
+    assert tiles == 213
+    rounds = two_rounds(pairs)
+    for chunks, _ in rounds:
+        _, off = pack(chunks)
+        for t in range(tiles):
+            lo, hi = 64 * t, min(64 * t + 64, len(chunks))
+            assert int(off[hi]) - int(off[lo]) > STAGE
+    st = run_rounds(codec, rounds)
+    assert (st[0] == qhuff.DEC_MORE).all() and (st[1] == qhuff.DEC_OK).all()
+
+
 @pytest.mark.gpu
 def test_kats_at_every_cut(codec):
     k17, k283, k2807 = load_kats()
