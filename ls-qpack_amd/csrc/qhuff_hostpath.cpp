@@ -1,0 +1,923 @@
+// qhuff_hostpath.cpp -- the pinned host-memory path of the C-ABI, buffer
+// registration and the per-string mirrors of the reference entry points.
+#include "qhuff_ctx.h"
+
+namespace qhuff {
+// qhuff_frames.cpp: a VALUE literal's static-table name length, or 0
+uint32_t field_ref_name_len(const uint8_t *buf, const struct qhuff_literal &l);
+}
+
+// Host copy workers for the PCIe-inclusive path: a staging memcpy of tens
+// of MB runs at one core's copy rate, so the pinned staging copies (and the
+// out_off rebasing) are split into slices run by a few persistent threads.
+struct CopyPool
+{
+    std::vector<std::thread> th;
+    std::mutex mu;
+    std::condition_variable go, done;
+    std::function<void(unsigned)> job;
+    unsigned slices = 0;
+    std::atomic<unsigned> next{0};
+    unsigned finished = 0;
+    unsigned active = 0;                 // workers inside a claim loop
+    uint64_t gen = 0;
+    bool stop = false;
+
+    explicit CopyPool(unsigned n)
+    {
+        for (unsigned i = 0; i < n; ++i)
+            th.emplace_back([this] { worker(); });
+    }
+    ~CopyPool()
+    {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            stop = true;
+        }
+        go.notify_all();
+        for (auto &t : th)
+            t.join();
+    }
+    void worker()
+    {
+        uint64_t seen = 0;
+        for (;;)
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            go.wait(lk, [&] { return stop || gen != seen; });
+            if (stop)
+                return;
+            seen = gen;
+            ++active;
+            const unsigned ns = slices;
+            lk.unlock();
+            unsigned k;
+            while ((k = next.fetch_add(1)) < ns)
+            {
+                job(k);
+                std::lock_guard<std::mutex> g(mu);
+                ++finished;
+            }
+            std::lock_guard<std::mutex> g(mu);
+            --active;
+            done.notify_all();
+        }
+    }
+    // run fn(0 .. n-1) on the workers and the calling thread; returns when
+    // every slice is done
+    void run(unsigned n, std::function<void(unsigned)> fn)
+    {
+        if (n == 0)
+            return;
+        if (th.empty() || n == 1)
+        {
+            for (unsigned k = 0; k < n; ++k)
+                fn(k);
+            return;
+        }
+        {
+            std::lock_guard<std::mutex> g(mu);
+            job = std::move(fn);
+            slices = n;
+            finished = 0;
+            next.store(0);
+            ++gen;
+        }
+        go.notify_all();
+        unsigned k;
+        while ((k = next.fetch_add(1)) < n)
+        {
+            job(k);
+            std::lock_guard<std::mutex> g(mu);
+            ++finished;
+        }
+        // every slice done AND no worker still inside its claim loop: a
+        // straggler's late fetch_add can then not race the next run()'s
+        // reset of job / slices / next (it reads `ns`, its own copy)
+        std::unique_lock<std::mutex> lk(mu);
+        done.wait(lk, [&] { return finished == n && active == 0; });
+    }
+    // memcpy split into ~1 MB slices
+    void copy(void *dst, const void *src, size_t n)
+    {
+        const size_t sl = 1u << 20;
+        const unsigned k = (unsigned) ((n + sl - 1) / sl);
+        run(k, [=](unsigned i) {
+            const size_t a = (size_t) i * sl, b = a + sl < n ? a + sl : n;
+            memcpy((uint8_t *) dst + a, (const uint8_t *) src + a, b - a);
+        });
+    }
+};
+
+// ---- host-memory path ------------------------------------------------------
+
+static int
+ensure_stage(qhuff_ctx *c, size_t bytes)
+{
+    if (bytes > c->h_stage_cap)
+    {
+        if (c->h_stage)
+            (void) hipHostFree(c->h_stage);
+        c->h_stage = nullptr;
+        c->h_stage_cap = 0;
+        HIPCHK(c, hipHostMalloc((void **) &c->h_stage, bytes));
+        c->h_stage_cap = bytes;
+    }
+    if (bytes > c->d_stage_cap)
+    {
+        if (c->d_stage)
+            (void) hipFree(c->d_stage);
+        c->d_stage = nullptr;
+        c->d_stage_cap = 0;
+        HIPCHK(c, hipMalloc((void **) &c->d_stage, bytes));
+        c->d_stage_cap = bytes;
+    }
+    return QHUFF_OK;
+}
+
+static inline size_t
+up16(size_t x)
+{
+    return (x + 15) & ~(size_t) 15;
+}
+
+static int
+pipe_setup(qhuff_ctx *c)
+{
+    if (c->pipe_ready)
+        return QHUFF_OK;
+    HIPCHK(c, hipStreamCreateWithFlags(&c->h2d_stream, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
+    for (unsigned i = 0; i < kMaxChunks; ++i)
+    {
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_k[i], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming));
+    }
+    unsigned t = 8;
+    if (const char *e = getenv("QHUFF_HOST_THREADS"))
+        t = (unsigned) strtoul(e, nullptr, 0);
+    if (t > 64)
+        t = 64;
+    c->pool = new CopyPool(t > 1 ? t - 1 : 0);   // + the calling thread
+    c->pipe_ready = true;
+    return QHUFF_OK;
+}
+
+// what pipe_setup made (qhuff_close)
+void
+qhuff::pipe_teardown(qhuff_ctx *c)
+{
+    if (c->pipe_ready)
+    {
+        (void) hipStreamDestroy(c->h2d_stream);
+        (void) hipStreamDestroy(c->d2h_stream);
+        for (unsigned i = 0; i < kMaxChunks; ++i)
+        {
+            (void) hipEventDestroy(c->ev_in[i]);
+            (void) hipEventDestroy(c->ev_k[i]);
+            (void) hipEventDestroy(c->ev_out[i]);
+        }
+    }
+    delete c->pool;
+}
+
+// The variant the kernels' own rules call for on a batch whose offsets the
+// host holds (the host-memory paths): the full kernel when a string is
+// longer than kHintLen bytes (decode: the cooperative threshold, kCoopMin
+// Huffman bytes; encode: a payload the full emit copies with the whole
+// wave, at ~8 bits a byte) or a 64-string tile spans more than the 3 KB
+// stage can take (a big tile).  One pass over the offsets on the copy
+// workers.  VERDICT r04 item 2: the device-pointer calls can only go by
+// history; these need not.
+constexpr uint32_t kHintLen = 128;
+constexpr uint32_t kHintSpan = 3072 - 32;
+// strings [a, b) of one tile
+static inline bool
+tile_rare(const uint32_t *off, uint32_t a, uint32_t b)
+{
+    bool r = off[b] - off[a] > kHintSpan;
+    for (uint32_t i = a; i < b; ++i)
+        r |= off[i + 1] - off[i] > kHintLen;
+    return r;
+}
+
+static bool
+host_rare(qhuff_ctx *c, const uint32_t *off, uint32_t n)
+{
+    std::atomic<bool> rare{false};
+    const uint32_t tiles = (n + 63) / 64, per = 1024;   // tiles per slice
+    c->pool->run((tiles + per - 1) / per, [&](unsigned k) {
+        const uint32_t t0 = k * per, t1 = t0 + per < tiles ? t0 + per : tiles;
+        bool r = false;
+        for (uint32_t t = t0; t < t1 && !r; ++t)
+        {
+            const uint32_t a = 64 * t, b = a + 64 < n ? a + 64 : n;
+            r = tile_rare(off, a, b);
+        }
+        if (r)
+            rare.store(true, std::memory_order_relaxed);
+    });
+    return rare.load();
+}
+
+static void
+host_hint(qhuff_ctx *c, bool enc, const uint32_t *off, uint32_t n)
+{
+    if (c->kernels == 0)
+        c->hint[enc ? 0 : 1] = host_rare(c, off, n) ? 1 : 0;
+}
+
+extern "C" int
+qhuff_batch_needs_full(const uint32_t *off, uint32_t n)
+{
+    if (!off)
+        return QHUFF_EINVAL;
+    for (uint32_t a = 0; a < n; a += 64)
+    {
+        if (tile_rare(off, a, a + 64 < n ? a + 64 : n))
+            return 1;
+    }
+    return 0;
+}
+
+// ---- caller buffers registered for direct DMA (qhuff_host_register) -------
+//
+// The host path stages the caller's input into pinned memory and its output
+// back out of it: ~67 MB of host memcpy for a 1M-string encode + decode,
+// which bounds it near the copy workers' rate (~22 GB/s of payload each way,
+// DESIGN.md section 5).  Buffers the caller registered once (hipHostRegister,
+// portable: every device's DMA engines reach them) are read and written by
+// the transfers directly: no staging copy, and the path is bound by PCIe.
+struct HostReg
+{
+    std::mutex mu;
+    std::vector<std::pair<uintptr_t, uintptr_t>> r;      // [begin, end)
+};
+static HostReg g_reg;
+
+bool
+qhuff::host_registered(const void *p, uint64_t bytes)
+{
+    if (!bytes)
+        return true;
+    const uintptr_t a = (uintptr_t) p, b = a + bytes;
+    std::lock_guard<std::mutex> g(g_reg.mu);
+    for (const auto &x : g_reg.r)
+        if (x.first <= a && b <= x.second)
+            return true;
+    return false;
+}
+
+extern "C" int
+qhuff_host_register(void *ptr, size_t bytes)
+{
+    if (!ptr || !bytes)
+        return QHUFF_EINVAL;
+    std::lock_guard<std::mutex> g(g_reg.mu);
+    for (const auto &x : g_reg.r)
+        if (x.first == (uintptr_t) ptr)
+            return QHUFF_EINVAL;         // (already registered)
+    const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterPortable);
+    if (e != hipSuccess)
+    {
+        (void) hipGetLastError();
+        snprintf(t_open_err, sizeof(t_open_err), "hipHostRegister: %s",
+                 hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? QHUFF_ENOMEM : QHUFF_EDEVICE;
+    }
+    g_reg.r.emplace_back((uintptr_t) ptr, (uintptr_t) ptr + bytes);
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_host_unregister(void *ptr)
+{
+    std::lock_guard<std::mutex> g(g_reg.mu);
+    for (size_t i = 0; i < g_reg.r.size(); ++i)
+        if (g_reg.r[i].first == (uintptr_t) ptr)
+        {
+            const hipError_t e = hipHostUnregister(ptr);
+            g_reg.r.erase(g_reg.r.begin() + (ptrdiff_t) i);
+            if (e != hipSuccess)
+            {
+                (void) hipGetLastError();
+                return QHUFF_EDEVICE;
+            }
+            return QHUFF_OK;
+        }
+    return QHUFF_EINVAL;
+}
+
+// The PCIe-inclusive path as a chunked pipeline.  The batch is cut into K
+// string ranges; per chunk: pinned staging copy (copy workers) -> H2D on the
+// upload stream -> kernel on the context stream (its out_off / status come
+// back on the same stream) -> once the chunk's size is known, D2H of exactly
+// its output bytes on the download stream -> copy out + rebase out_off on
+// the host.  Chunk i's host copies overlap chunk i-1's kernel and transfers.
+// Kernels stay serialised on one stream (one look-back workspace).
+//
+// Stage layout (pinned and device alike): [in bytes | in_off (n + 1) |
+// out: per-chunk bound regions | out_off: n_i + 1 per chunk | status n].
+// The kernels read the original offsets: `in` is passed rebased by -in_off[0].
+//
+// Shard k of a multi-context call (qhuff_*_batch_host_multi, `sync`): the
+// shard's output goes to `out` at a base only known once every earlier shard
+// has sized its output, so its copies out of the pinned stage wait until
+// all its chunks are fetched and the base is published -- its uploads,
+// kernels and downloads never wait for another shard.
+int
+qhuff::host_batch(qhuff_ctx *c, bool enc, const uint8_t *in, const uint32_t *in_off,
+           uint32_t n, unsigned mode, uint8_t *out, uint32_t *out_off,
+           uint8_t *status, ShardSync *sync, unsigned shard, bool last_shard,
+           bool out_reg)
+{
+    if (!c || !in_off || !out_off || (n && (!in || !out)) || (!enc && n && !status))
+        return QHUFF_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = pipe_setup(c);
+    if (rc)
+        return rc;
+    const uint64_t a0 = in_off[0], in_bytes = (uint64_t) in_off[n] - a0;
+    // chunks of >= 2^chunk_shift bytes of input (QHUFF_HOST_CHUNK_SHIFT;
+    // default 8 MB: measured on MI355X, 1M strings, 8 copy threads -- 2 MB
+    // chunks 2.9 / 2.7 ms enc / dec, 4 MB 2.2 / 2.0, 8 MB 1.8 / 1.7, 16 MB
+    // 1.9 / 2.3; tools/host_path_probe.py), at most kMaxChunks
+    static const unsigned chunk_shift = [] {
+        const char *e = getenv("QHUFF_HOST_CHUNK_SHIFT");
+        const unsigned v = e ? (unsigned) strtoul(e, nullptr, 0) : 23u;
+        return v >= 16 && v <= 30 ? v : 23u;
+    }();
+    unsigned K = (unsigned) (in_bytes >> chunk_shift);
+    K = K < 1 ? 1 : (K > kMaxChunks ? kMaxChunks : K);
+    if (K > n)
+        K = n ? n : 1;
+    uint32_t cut[kMaxChunks + 1];
+    uint64_t ob[kMaxChunks + 1];                 // out region starts
+    ob[0] = 0;
+    for (unsigned i = 0; i <= K; ++i)
+        cut[i] = (uint32_t) ((uint64_t) n * i / K);
+    for (unsigned i = 0; i < K; ++i)
+    {
+        const uint32_t s0 = cut[i], s1 = cut[i + 1];
+        const uint64_t b = (uint64_t) in_off[s1] - in_off[s0];
+        ob[i + 1] = ob[i] + up16(bound_of(enc, b, s1 - s0, mode));
+    }
+    if (ob[K] > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const size_t o_in = 0, o_off = up16(in_bytes);
+    const size_t o_out = o_off + up16(4ull * (n + 1));
+    const size_t o_oo = o_out + ob[K];
+    const size_t o_st = o_oo + up16(4ull * (n + K));
+    const size_t total = o_st + up16(n ? n : 1);
+    rc = ensure_stage(c, total);
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t sk = c->own_stream;
+    uint64_t base = 0;                           // output bytes so far
+    uint32_t tot[kMaxChunks];
+    uint64_t obase[kMaxChunks];                  // chunk i's output start
+    uint64_t fbase = 0;                          // (relative to the call's)
+    // a small batch brings its whole output bound back right behind the
+    // kernel: one synchronisation instead of two (latency, not bandwidth)
+    const bool small = K == 1 && ob[1] <= (4u << 20);
+    // caller buffers registered for DMA (qhuff_host_register): transferred
+    // directly, no staging copy
+    const bool din = host_registered(in + a0, in_bytes)
+                  && host_registered(in_off, 4ull * (n + 1));
+    // (a shard of a multi-context call writes at out + its base, beyond its
+    // own bound from `out`: out_reg is host_multi's verdict over the whole
+    // call's bound, the range the shards can write)
+    const bool dout = !small
+        && (sync ? out_reg
+                 : host_registered(out, bound_of(enc, in_bytes, n, mode)))
+        && host_registered(out_off, 4ull * (n + 1))
+        && (enc || host_registered(status, n));
+
+    auto stage_in = [&](unsigned i) -> int {
+        const uint32_t s0 = cut[i], s1 = cut[i + 1];
+        const uint64_t b0 = in_off[s0] - a0, b1 = in_off[s1] - a0;
+        const uint8_t *src_in = in + a0;
+        const uint8_t *src_off = (const uint8_t *) in_off;
+        if (!din)
+        {
+            c->pool->copy(H + o_in + b0, in + a0 + b0, b1 - b0);
+            memcpy(H + o_off + 4ull * s0, in_off + s0, 4ull * (s1 - s0 + 1));
+            src_in = H + o_in;
+            src_off = H + o_off;
+        }
+        HIPCHK(c, hipMemcpyAsync(D + o_in + b0, src_in + b0, b1 - b0,
+                                 hipMemcpyHostToDevice, c->h2d_stream));
+        HIPCHK(c, hipMemcpyAsync(D + o_off + 4ull * s0, src_off + 4ull * s0,
+                                 4ull * (s1 - s0 + 1), hipMemcpyHostToDevice,
+                                 c->h2d_stream));
+        HIPCHK(c, hipEventRecord(c->ev_in[i], c->h2d_stream));
+        HIPCHK(c, hipStreamWaitEvent(sk, c->ev_in[i], 0));
+        const uint8_t *din = D + o_in - a0;      // kernels see original offsets
+        const uint32_t *doff = (const uint32_t *) (D + o_off) + s0;
+        uint32_t *doo = (uint32_t *) (D + o_oo) + s0 + i;
+        host_hint(c, enc, in_off + s0, s1 - s0);
+        int r = enc ? qhuff_encode_batch(c, din, doff, s1 - s0, mode,
+                                         D + o_out + ob[i], doo, sk)
+                    : qhuff_decode_batch(c, din, doff, s1 - s0,
+                                         D + o_out + ob[i], doo, D + o_st + s0,
+                                         sk);
+        if (r)
+            return r;
+        if (dout)
+        {
+            // the chunk-local offsets straight into out_off (rebased in
+            // place by unstage), the chunk's total into the stage
+            HIPCHK(c, hipMemcpyAsync(out_off + s0, doo, 4ull * (s1 - s0),
+                                     hipMemcpyDeviceToHost, sk));
+            HIPCHK(c, hipMemcpyAsync(H + o_oo + 4ull * (s1 + i), doo + (s1 - s0),
+                                     4, hipMemcpyDeviceToHost, sk));
+            if (!enc)
+                HIPCHK(c, hipMemcpyAsync(status + s0, D + o_st + s0, s1 - s0,
+                                         hipMemcpyDeviceToHost, sk));
+        }
+        else
+        {
+            HIPCHK(c, hipMemcpyAsync(H + o_oo + 4ull * (s0 + i), doo,
+                                     4ull * (s1 - s0 + 1), hipMemcpyDeviceToHost,
+                                     sk));
+            if (!enc)
+                HIPCHK(c, hipMemcpyAsync(H + o_st + s0, D + o_st + s0, s1 - s0,
+                                         hipMemcpyDeviceToHost, sk));
+        }
+        if (small)
+            HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, ob[1],
+                                     hipMemcpyDeviceToHost, sk));
+        HIPCHK(c, hipEventRecord(c->ev_k[i], sk));
+        return QHUFF_OK;
+    };
+    // chunk i's output bytes back: to the stage, or (dout) straight to
+    // out + dst (once its base is known)
+    auto issue_out = [&](unsigned i, uint64_t dst) -> int {
+        HIPCHK(c, hipStreamWaitEvent(c->d2h_stream, c->ev_k[i], 0));
+        if (tot[i])
+            HIPCHK(c, hipMemcpyAsync(dout ? out + dst : H + o_out + ob[i],
+                                     D + o_out + ob[i], tot[i],
+                                     hipMemcpyDeviceToHost, c->d2h_stream));
+        HIPCHK(c, hipEventRecord(c->ev_out[i], c->d2h_stream));
+        return QHUFF_OK;
+    };
+    auto fetch = [&](unsigned i) -> int {
+        HIPCHK(c, hipEventSynchronize(c->ev_k[i]));
+        const uint32_t s1 = cut[i + 1];
+        tot[i] = ((const uint32_t *) (H + o_oo))[s1 + i];
+        obase[i] = fbase;
+        fbase += tot[i];
+        if (small)
+            return QHUFF_OK;                     // already here
+        // (a shard of a multi-context call learns its base only later: its
+        // direct copies out wait for it)
+        if (dout && sync)
+            return QHUFF_OK;
+        return issue_out(i, obase[i]);
+    };
+    auto unstage = [&](unsigned i) -> int {
+        if (!small)
+            HIPCHK(c, hipEventSynchronize(c->ev_out[i]));
+        const uint32_t s0 = cut[i], s1 = cut[i + 1];
+        if (dout)
+        {
+            // bytes and statuses are in place; the offsets get the base
+            const uint32_t bs = (uint32_t) base;
+            const uint32_t m = s1 - s0, sl = 1u << 16;
+            if (bs)
+                c->pool->run((m + sl - 1) / sl, [=](unsigned k) {
+                    const uint32_t a = k * sl, b = a + sl < m ? a + sl : m;
+                    for (uint32_t j = a; j < b; ++j)
+                        out_off[s0 + j] += bs;
+                });
+            base += tot[i];
+            return QHUFF_OK;
+        }
+        c->pool->copy(out + base, H + o_out + ob[i], tot[i]);
+        const uint32_t *ho = (const uint32_t *) (H + o_oo) + s0 + i;
+        const uint32_t bs = (uint32_t) base;
+        const uint32_t m = s1 - s0, sl = 1u << 16;
+        c->pool->run((m + sl - 1) / sl, [=](unsigned k) {
+            const uint32_t a = k * sl, b = a + sl < m ? a + sl : m;
+            for (uint32_t j = a; j < b; ++j)
+                out_off[s0 + j] = bs + ho[j];
+        });
+        if (!enc)
+            memcpy(status + s0, H + o_st + s0, m);
+        base += tot[i];
+        return QHUFF_OK;
+    };
+
+    if (n == 0)
+    {
+        if (sync)
+        {
+            sync->publish(shard, 0);
+            base = sync->base_of(shard);
+            if (base == ~0ull)
+                return QHUFF_EDEVICE;
+        }
+        if (last_shard)
+            out_off[0] = (uint32_t) base;
+        return QHUFF_OK;
+    }
+    if (sync)
+    {
+        // every chunk in flight first, then the copies out at the base
+        for (unsigned i = 0; i < K; ++i)
+        {
+            if ((rc = stage_in(i)))
+                return rc;
+            if (i >= 1 && (rc = fetch(i - 1)))
+                return rc;
+        }
+        if ((rc = fetch(K - 1)))
+            return rc;
+        uint64_t t = 0;
+        for (unsigned i = 0; i < K; ++i)
+            t += tot[i];
+        sync->publish(shard, t);
+        base = sync->base_of(shard);
+        if (base == ~0ull)
+            return QHUFF_EDEVICE;
+        if (dout && !small)
+            for (unsigned i = 0; i < K; ++i)
+                if ((rc = issue_out(i, base + obase[i])))
+                    return rc;
+        for (unsigned i = 0; i < K; ++i)
+            if ((rc = unstage(i)))
+                return rc;
+    }
+    else
+    {
+        for (unsigned i = 0; i < K; ++i)
+        {
+            if ((rc = stage_in(i)))
+                return rc;
+            if (i >= 1 && (rc = fetch(i - 1)))
+                return rc;
+            if (i >= 2 && (rc = unstage(i - 2)))
+                return rc;
+        }
+        if ((rc = fetch(K - 1)))
+            return rc;
+        for (unsigned i = K >= 2 ? K - 2 : 0; i < K; ++i)
+            if ((rc = unstage(i)))
+                return rc;
+    }
+    // (a shard's closing offset is the next shard's first one: written by
+    // the last shard only)
+    if (last_shard)
+        out_off[n] = (uint32_t) base;
+    {
+        if ((rc = mirror_error(c)))
+            return rc;
+    }
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_encode_batch_host(qhuff_ctx *c, const uint8_t *in,
+                        const uint32_t *in_off, uint32_t n, unsigned mode,
+                        uint8_t *out, uint32_t *out_off)
+{
+    if (!mode_ok(mode))
+        return QHUFF_EINVAL;
+    // with a service attached the context may be shared between threads
+    // (qhuff_lsqpack_set_context): every call goes through svc_call, which
+    // serialises the ones too large for a slot on the context's host path
+    // (host_batch shares the context's staging buffers, streams and events)
+    if (c && c->svc)
+        return svc_call(c->svc, true, in, in_off, n, mode, out, out_off, nullptr);
+    return host_batch(c, true, in, in_off, n, mode, out, out_off, nullptr);
+}
+
+extern "C" int
+qhuff_decode_batch_host(qhuff_ctx *c, const uint8_t *in,
+                        const uint32_t *in_off, uint32_t n, uint8_t *out,
+                        uint32_t *out_off, uint8_t *status)
+{
+    if (c && c->svc)                      // (see qhuff_encode_batch_host)
+        return svc_call(c->svc, false, in, in_off, n, 0, out, out_off, status);
+    return host_batch(c, false, in, in_off, n, 0, out, out_off, status);
+}
+
+// Host pointers: one staged round trip on the context's stream.  Stage
+// layout: [in | in_off | flags | state | out_off | status | out].
+extern "C" int
+qhuff_decode_stream_host(qhuff_ctx *c, const uint8_t *in,
+                         const uint32_t *in_off, uint32_t n,
+                         struct qhuff_decode_status *state,
+                         const uint8_t *flags, uint8_t *out,
+                         uint32_t *out_off, uint8_t *status)
+{
+    if (!c || !in_off || !out_off || (n && (!in || !out || !status || !state)))
+        return QHUFF_EINVAL;
+    if (n == 0)
+    {
+        out_off[0] = 0;
+        return QHUFF_OK;
+    }
+    if (in_off[n] < in_off[0])
+        return QHUFF_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t a0 = in_off[0], in_bytes = (uint64_t) in_off[n] - a0;
+    const uint64_t bound = qhuff_decode_stream_bound(in_bytes, n);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const size_t o_off = up16(in_bytes) + 16;
+    const size_t o_fl = o_off + up16(4ull * (n + 1));
+    const size_t o_state = o_fl + up16(n);
+    const size_t o_oo = o_state + up16(2ull * n);
+    const size_t o_st = o_oo + up16(4ull * (n + 1));
+    const size_t o_out = o_st + up16(n);
+    int rc = ensure_stage(c, o_out + up16(bound));
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t sk = c->own_stream;
+    memcpy(H, in + a0, in_bytes);
+    memcpy(H + o_off, in_off, 4ull * (n + 1));
+    if (flags)
+        memcpy(H + o_fl, flags, n);
+    memcpy(H + o_state, state, 2ull * n);
+    HIPCHK(c, hipMemcpyAsync(D, H, o_oo, hipMemcpyHostToDevice, sk));
+    // (the kernel reads the caller's offsets: `in` rebased by -in_off[0])
+    rc = qhuff_decode_stream(c, D - a0, (const uint32_t *) (D + o_off), n,
+                             (struct qhuff_decode_status *) (D + o_state),
+                             flags ? D + o_fl : nullptr, D + o_out,
+                             (uint32_t *) (D + o_oo), D + o_st, sk);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(H + o_state, D + o_state, o_out - o_state,
+                             hipMemcpyDeviceToHost, sk));
+    HIPCHK(c, hipStreamSynchronize(sk));
+    rc = mirror_error(c);
+    if (rc)
+        return rc;
+    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
+    if (total)
+    {
+        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
+                                 hipMemcpyDeviceToHost, sk));
+        HIPCHK(c, hipStreamSynchronize(sk));
+        memcpy(out, H + o_out, total);
+    }
+    memcpy(state, H + o_state, 2ull * n);
+    memcpy(out_off, H + o_oo, 4ull * (n + 1));
+    memcpy(status, H + o_st, n);
+    return QHUFF_OK;
+}
+
+// ---- batched literal decode (pre-parsed spans, qhuff_frames.cpp) -----------
+
+extern "C" uint64_t
+qhuff_literals_bound(const struct qhuff_literal *lits, uint32_t n)
+{
+    uint64_t b = 16;
+    for (uint32_t i = 0; lits && i < n; ++i)
+        b += lits[i].huffman ? (uint64_t) lits[i].len * 8 / 5 : lits[i].len;
+    return b;
+}
+
+// Huffman payloads gathered straight into the pinned stage (one copy), one
+// decode launch for all of them, raw literals copied on the host meanwhile.
+// Stage layout: [huff bytes | in_off | out bytes | out_off | status].
+extern "C" int
+qhuff_decode_literals_host(qhuff_ctx *c, const uint8_t *buf,
+                           const struct qhuff_literal *lits, uint32_t n,
+                           uint8_t *out, uint32_t *out_off, uint8_t *status)
+{
+    return qhuff_decode_literals_ex(c, buf, lits, n, 0, out, out_off, status);
+}
+
+// max_len > 0: the field-section limit -- a string that decodes (or is
+// declared, raw) longer than LSXPACK_MAX_STRLEN is an error in the
+// reference (header_out_grow_buf, lsqpack.c:3350-3351; 3682-3685,
+// 3769-3772), whatever the kernel's status.
+extern "C" int
+qhuff_decode_literals_ex(qhuff_ctx *c, const uint8_t *buf,
+                         const struct qhuff_literal *lits, uint32_t n,
+                         uint32_t max_len, uint8_t *out, uint32_t *out_off,
+                         uint8_t *status)
+{
+    if (!c || !out_off || (n && (!buf || !lits || !out || !status)))
+        return QHUFF_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint64_t hb = 0;
+    uint32_t nh = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (lits[i].huffman)
+        {
+            hb += lits[i].len;
+            ++nh;
+        }
+    const uint64_t ob = qhuff_decode_bound(hb, nh);
+    if (ob > 0xffffffffull || hb > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const size_t o_off = up16(hb), o_out = o_off + up16(4ull * (nh + 1));
+    const size_t o_oo = o_out + up16(ob), o_st = o_oo + up16(4ull * (nh + 1));
+    const size_t total = o_st + up16(nh ? nh : 1);
+    int rc = ensure_stage(c, total);
+    if (rc)
+        return rc;
+    hipStream_t st = c->own_stream;
+    uint32_t *hoff = (uint32_t *) (c->h_stage + o_off);
+    {
+        uint32_t k = 0, a = 0;
+        for (uint32_t i = 0; i < n; ++i)
+            if (lits[i].huffman)
+            {
+                memcpy(c->h_stage + a, buf + lits[i].pos, lits[i].len);
+                hoff[k++] = a;
+                a += lits[i].len;
+            }
+        hoff[k] = a;
+    }
+    if (nh)
+    {
+        // the variant from this batch (auto mode only: a pinned variant
+        // needs neither the copy workers nor the scan)
+        if (c->kernels == 0)
+        {
+            if (!c->pipe_ready && (rc = pipe_setup(c)))
+                return rc;
+            host_hint(c, false, hoff, nh);
+        }
+        HIPCHK(c, hipMemcpyAsync(c->d_stage, c->h_stage, o_out,
+                                 hipMemcpyHostToDevice, st));
+        rc = qhuff_decode_batch(c, c->d_stage, (const uint32_t *) (c->d_stage
+                                + o_off), nh, c->d_stage + o_out,
+                                (uint32_t *) (c->d_stage + o_oo),
+                                c->d_stage + o_st, st);
+        if (rc)
+            return rc;
+        if (o_st + nh - o_out <= (4u << 20))
+        {
+            // small: the decoded bytes' bound, sizes and status in one copy
+            HIPCHK(c, hipMemcpyAsync(c->h_stage + o_out, c->d_stage + o_out,
+                                     o_st + nh - o_out, hipMemcpyDeviceToHost,
+                                     st));
+            HIPCHK(c, hipStreamSynchronize(st));
+        }
+        else
+        {
+            // sizes and status first, then exactly the decoded bytes
+            HIPCHK(c, hipMemcpyAsync(c->h_stage + o_oo, c->d_stage + o_oo,
+                                     4ull * (nh + 1), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(c->h_stage + o_st, c->d_stage + o_st, nh,
+                                     hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            const uint32_t dec_total = ((const uint32_t *) (c->h_stage + o_oo))[nh];
+            HIPCHK(c, hipMemcpyAsync(c->h_stage + o_out, c->d_stage + o_out,
+                                     dec_total, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+        }
+        if ((rc = mirror_error(c)))
+            return rc;
+    }
+    const uint32_t *doo = (const uint32_t *) (c->h_stage + o_oo);
+    const uint8_t *dst = c->h_stage + o_st;
+    uint64_t o = 0;
+    uint32_t k = 0;
+    // max_len (field sections): the reference decodes a field line's name
+    // and value into ONE header buffer, which never grows past
+    // LSXPACK_MAX_STRLEN (header_out_grow_buf, lsqpack.c:3346-3351; its
+    // size is a uint16 lsxpack_strlen_t): a name decoded here (NAME literal
+    // of the same instruction) or a static-table name (field_ref_name_len)
+    // counts against its value.  A dynamic-table name is not known to the
+    // framing: that value is checked alone.
+    uint32_t name_len = 0, name_instr = 0;
+    bool have_name = false;
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        out_off[i] = (uint32_t) o;
+        uint32_t len = lits[i].len;
+        uint8_t stv = QHUFF_DEC_OK;
+        const uint8_t *src = buf + lits[i].pos;
+        if (lits[i].huffman)
+        {
+            const uint32_t a = doo[k], b = doo[k + 1];
+            stv = dst[k];
+            ++k;
+            len = b - a;
+            src = c->h_stage + o_out + a;
+        }
+        uint32_t lim_used = 0;
+        if (max_len && lits[i].kind == QHUFF_LIT_VALUE)
+            lim_used = have_name && name_instr == lits[i].instr
+                     ? name_len : field_ref_name_len(buf, lits[i]);
+        have_name = false;
+        if (max_len && (uint64_t) lim_used + len > max_len)
+            stv = QHUFF_DEC_ERROR;
+        status[i] = stv;
+        if (stv != QHUFF_DEC_OK)
+            continue;
+        if (lits[i].kind == QHUFF_LIT_NAME)
+        {
+            have_name = true;
+            name_len = len;
+            name_instr = lits[i].instr;
+        }
+        memcpy(out + o, src, len);
+        o += len;
+    }
+    out_off[n] = (uint32_t) o;
+    return QHUFF_OK;
+}
+
+// ---- header hashing, host buffers ----------------------------------------------
+
+// Stage layout: [name/value bytes | offsets (2n + 1) | name_hash | nameval_hash].
+// The kernel reads the caller's offsets unchanged: `in` is passed rebased by
+// -off[0].
+extern "C" int
+qhuff_xxh32_headers_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                         uint32_t n, uint32_t seed, uint32_t *name_hash,
+                         uint32_t *nameval_hash)
+{
+    if (!c || !off || (n && (!in || !name_hash || !nameval_hash)))
+        return QHUFF_EINVAL;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    if (n == 0)
+        return QHUFF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
+    const size_t o_off = up16(bytes), o_h1 = o_off + up16(4ull * (2ull * n + 1));
+    const size_t o_h2 = o_h1 + up16(4ull * n), total = o_h2 + up16(4ull * n);
+    int rc = ensure_stage(c, total);
+    if (rc)
+        return rc;
+    hipStream_t st = c->own_stream;
+    memcpy(c->h_stage, in + a0, bytes);
+    memcpy(c->h_stage + o_off, off, 4ull * (2ull * n + 1));
+    HIPCHK(c, hipMemcpyAsync(c->d_stage, c->h_stage, o_h1,
+                             hipMemcpyHostToDevice, st));
+    rc = qhuff_xxh32_headers(c, c->d_stage - a0,
+                             (const uint32_t *) (c->d_stage + o_off), n, seed,
+                             (uint32_t *) (c->d_stage + o_h1),
+                             (uint32_t *) (c->d_stage + o_h2), st);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_stage + o_h1, c->d_stage + o_h1,
+                             total - o_h1, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(name_hash, c->h_stage + o_h1, 4ull * n);
+    memcpy(nameval_hash, c->h_stage + o_h2, 4ull * n);
+    return QHUFF_OK;
+}
+
+// ---- per-string mirrors -----------------------------------------------------
+
+extern "C" int
+qhuff_enc_enc_str(qhuff_ctx *c, unsigned prefix_bits, unsigned char *dst,
+                  size_t dst_len, const unsigned char *str, unsigned str_len)
+{
+    if (!c || !dst || (!str && str_len) || (prefix_bits != 3
+            && prefix_bits != 5 && prefix_bits != 7))
+        return -1;
+    uint32_t off[2] = {0, str_len};
+    uint64_t bound = qhuff_encode_bound(str_len, 1, prefix_bits);
+    unsigned char *tmp = (unsigned char *) malloc(bound);
+    unsigned char dummy = 0;
+    uint32_t oo[2];
+    if (!tmp)
+        return -1;
+    int rc = qhuff_encode_batch_host(c, str_len ? str : &dummy, off, 1,
+                                     prefix_bits, tmp, oo);
+    int r = -1;
+    if (rc == QHUFF_OK && oo[1] <= dst_len)
+    {
+        // keep dst[0] bits above the H bit (lsqpack.c:852, 863)
+        unsigned char keep = dst[0] & (unsigned char) ~((1u << (prefix_bits + 1)) - 1);
+        memcpy(dst, tmp, oo[1]);
+        dst[0] |= keep;
+        r = (int) oo[1];
+    }
+    free(tmp);
+    return r;
+}
+
+extern "C" unsigned
+qhuff_enc_str_size(qhuff_ctx *c, const unsigned char *str, unsigned str_len)
+{
+    if (!c || (!str && str_len))
+        return 0;
+    uint32_t off[2] = {0, str_len};
+    uint64_t bound = qhuff_encode_bound(str_len, 1, 0);
+    unsigned char *tmp = (unsigned char *) malloc(bound);
+    unsigned char dummy = 0;
+    uint32_t oo[2] = {0, 0};
+    if (!tmp)
+        return 0;
+    int rc = qhuff_encode_batch_host(c, str_len ? str : &dummy, off, 1, 0, tmp,
+                                     oo);
+    free(tmp);
+    return rc == QHUFF_OK ? oo[1] : 0;
+}
+
+// qhuff_huff_decode_ex (lsqpack_huff_decode with its full signature): see
+// qhuff_shim.cpp

@@ -1,5 +1,5 @@
 // qhuff_kernels.h -- argument blocks and launch entry points shared by the
-// kernel translation units and the host C-ABI (qhuff_host.cpp).
+// kernel translation units and the host C-ABI files (qhuff_ctx.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -65,7 +65,7 @@ struct HashArgs
     uint32_t pairs;
 };
 
-// ---- low-latency service (qhuff_service.hip, qhuff_svc_* in qhuff_host.cpp)
+// ---- low-latency service (qhuff_service.hip, qhuff_svc_host.cpp) ----------
 //
 // One request slot per service wave, in pinned host memory mapped into the
 // device (fine-grained): the host writes a request and then its sequence
@@ -184,7 +184,7 @@ int encode_waves_per_block();
 int decode_waves_per_block();
 uint32_t decode_tile_strings();            // strings per decode tile
 hipError_t launch_service(const SvcArgs &a, uint32_t grid, hipStream_t st);
-bool ctx_has_service(const qhuff_ctx *c);   // (qhuff_host.cpp)
+bool ctx_has_service(const qhuff_ctx *c);   // (qhuff_svc_host.cpp)
 int decode_keep_rejected(qhuff_ctx *c, const uint8_t *in,
                          const uint32_t *in_off, uint32_t n, uint8_t *out,
                          uint32_t *out_off, uint8_t *status);

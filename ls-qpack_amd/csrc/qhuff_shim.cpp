@@ -25,7 +25,7 @@
 #include "qhuff_tables.h"
 
 namespace qhuff {
-bool ctx_has_service(const qhuff_ctx *c);   // (qhuff_host.cpp)
+bool ctx_has_service(const qhuff_ctx *c);   // (qhuff_svc_host.cpp)
 int decode_keep_rejected(qhuff_ctx *c, const uint8_t *in,
                          const uint32_t *in_off, uint32_t n, uint8_t *out,
                          uint32_t *out_off, uint8_t *status);
@@ -274,9 +274,9 @@ qhuff_lsqpack_set_device(int device)
 extern "C" int
 qhuff_lsqpack_set_context(qhuff_ctx *ctx)
 {
-    // a shared context is thread-safe only through its service (qhuff_host.cpp
-    // svc_call): without one, concurrent calls would race on the context's
-    // host-path staging buffers and streams
+    // a shared context is thread-safe only through its service (svc_call,
+    // qhuff_svc_host.cpp): without one, concurrent calls would race on the
+    // context's host-path staging buffers and streams
     if (ctx && !qhuff::ctx_has_service(ctx))
         return QHUFF_EINVAL;
     g_shared.store(ctx, std::memory_order_release);

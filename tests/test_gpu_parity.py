@@ -492,7 +492,7 @@ def test_kernel_variant_switch():
 
 def test_host_path_variant_from_batch():
     """Host-memory calls choose the kernel variant from the batch itself
-    (qhuff_host.cpp host_hint: the offsets are on the host): after 10 token
+    (qhuff_hostpath.cpp host_hint: the offsets are on the host): after 10 token
     batches a batch with big tiles runs the full kernel on its first
     launch, and the next token batch the lean one again -- no history, no
     first-launch cliff (VERDICT r04 item 2 for the paths that can see their
