@@ -438,6 +438,64 @@ int qhuff_decode_literals_ex(qhuff_ctx *ctx, const uint8_t *buf,
                              uint32_t max_len, uint8_t *out, uint32_t *out_off,
                              uint8_t *status);
 
+/* ---- literals decoded in place from wire data ----------------------------
+ * qhuff_decode_literals_ex gathers every Huffman payload on the host, decodes
+ * the packed batch and interleaves the results with the raw literals on the
+ * host again; it has no device-pointer form.  qhuff_decode_wire takes the
+ * scanners' descriptors as they are: one descriptor a lane, the payloads read
+ * where they lie in the wire buffer, one launch.  The output of
+ * qhuff_encode_batch(..., QHUFF_ENC_LITERAL7, ...) is such a buffer too.
+ * QHUFF_FEATURE_WIRE and the symbols announce it (the ABI version is
+ * unchanged).
+ *
+ * For descriptors that satisfy the order rule, out, out_off[0 .. n] and
+ * status[0 .. n) are byte for byte those of qhuff_decode_literals_ex(ctx, buf,
+ * lits, n, max_len, ...): a Huffman literal decodes as in qhuff_decode_batch,
+ * a raw one is copied; with max_len != 0 a literal longer than max_len once
+ * decoded (or copied) gets QHUFF_DEC_ERROR and 0 bytes, a VALUE literal's
+ * length counted together with the decoded length of the NAME literal
+ * directly before it (same instr, status OK) or else with the static-table
+ * name its instruction refers to (01NT, T = 1); max_len = 0: no limit.
+ * `out` must hold qhuff_literals_bound(lits, n) bytes.
+ *
+ * Order rule -- THE CALLER'S DUTY for qhuff_decode_wire, whose descriptors
+ * are in device memory where the call cannot check them: the descriptors are
+ * in wire order and disjoint, pos[i] + len[i] <= pos[i + 1] (and within 32
+ * bits), with hdr_len <= pos and instr <= pos - hdr_len.  Both scanners emit
+ * descriptors of this form.  qhuff_literals_check (host only) tests it:
+ * QHUFF_OK, or QHUFF_EINVAL with *bad (may be NULL) = the first offending
+ * index -- of a pair out of order or overlapping, the second literal.
+ * qhuff_decode_wire_host runs the check itself (QHUFF_EINVAL).
+ *
+ * The buffer contract above applies.  Writes: out[0 .. out_off[n]),
+ * out_off[0 .. n], status[0 .. n), nothing else; for n = 0 only out_off[0].
+ * Reads: lits[0 .. n) and the 16-byte-aligned blocks that contain the wire
+ * bytes from lits[0].pos to lits[n-1].pos + lits[n-1].len, the bytes between
+ * the literals included; with max_len != 0 also the instruction bytes
+ * [instr, pos - hdr_len) of VALUE literals.  32-bit output offsets (the
+ * sticky QHUFF_DEVERR_RANGE) and launch timing (QHUFF_KIND_DECODE) as
+ * qhuff_decode_batch.  qhuff_decode_wire: device pointers (buf, lits, out,
+ * out_off, status), asynchronous on `stream`.  qhuff_decode_wire_host: host
+ * pointers, synchronous; QHUFF_ERANGE when the bound or the wire span passes
+ * 32 bits.  Every literal is decoded by one lane: there is no cooperative
+ * walk for long literals, and a 64-literal tile whose wire span passes 3 KB
+ * -- a long literal, or short ones far apart -- takes the lean kernels'
+ * out-of-line path; no speed is promised for those. */
+#define QHUFF_FEATURE_WIRE 1
+
+int qhuff_literals_check(const struct qhuff_literal *lits, uint32_t n,
+                         uint32_t *bad);
+
+int qhuff_decode_wire(qhuff_ctx *ctx, const uint8_t *buf,
+                      const struct qhuff_literal *lits, uint32_t n,
+                      uint32_t max_len, uint8_t *out, uint32_t *out_off,
+                      uint8_t *status, void *stream);
+
+int qhuff_decode_wire_host(qhuff_ctx *ctx, const uint8_t *buf,
+                           const struct qhuff_literal *lits, uint32_t n,
+                           uint32_t max_len, uint8_t *out, uint32_t *out_off,
+                           uint8_t *status);
+
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman
  * payload was precomputed by a QHUFF_ENC_PAYLOAD batch (huff, huff_len =

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "../../include/qhuff.h"
+#include "qhuff_names.h"
 
 namespace {
 
@@ -134,17 +135,7 @@ rc_of(int r)
 
 }  // namespace
 
-// Name lengths of the QPACK static table (RFC 9204 Appendix A; the
-// reference's static_table[], lsqpack.c:104-209 -- the list in
-// tests/golden/qpack_static_table.json, which test_frames.py checks this
-// against through qhuff_decode_literals_ex).
-static const uint8_t kStaticNameLen[99] = {
-    10, 5, 3, 19, 14, 6, 4, 4, 17, 13, 13, 4, 8, 7, 10, 7, 7, 7, 7, 7, 7, 7,
-    7, 7, 7, 7, 7, 7, 7, 6, 6, 15, 13, 28, 28, 27, 13, 13, 13, 13, 13, 13,
-    16, 16, 12, 12, 12, 12, 12, 12, 12, 12, 12, 12, 12, 5, 25, 25, 25, 4, 4,
-    22, 16, 7, 7, 7, 7, 7, 7, 7, 7, 7, 15, 32, 32, 28, 28, 28, 28, 29, 30,
-    29, 29, 7, 13, 23, 10, 9, 9, 8, 6, 7, 6, 19, 25, 10, 15, 15, 15};
-
+// (the static table's name lengths: qhuff_names.h, shared with the device)
 namespace qhuff {
 
 // The length of the name a field-section VALUE literal's instruction refers
@@ -164,7 +155,7 @@ field_ref_name_len(const uint8_t *buf, const struct qhuff_literal &l)
     if ((*p & 0xd0) != 0x50)                 // 01NT, T = 1
         return 0;
     uint32_t idx;
-    if (dec_int24(&p, end, 4, &idx) || idx >= sizeof(kStaticNameLen))
+    if (dec_int24(&p, end, 4, &idx) || idx >= kStaticNames)
         return 0;
     return kStaticNameLen[idx];
 }
@@ -360,4 +351,34 @@ qhuff_frame_literal(unsigned prefix_bits, unsigned char *dst, size_t dst_len,
     put_int(dst, n, prefix_bits);
     memcpy(dst + len_size, h ? huff : str, n);
     return (int) (len_size + n);
+}
+
+// The order rule of the in-place literal decode (qhuff_decode_wire,
+// qhuff_wire.hip): descriptors in wire order and disjoint, each with its
+// header and its instruction in front of it, every end within 32 bits.
+// Both scanners above emit descriptors of this form.
+extern "C" int
+qhuff_literals_check(const struct qhuff_literal *lits, uint32_t n,
+                     uint32_t *bad)
+{
+    if (!lits && n)
+        return QHUFF_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const qhuff_literal &l = lits[i];
+        const uint64_t end = (uint64_t) l.pos + l.len;
+        const bool ok = l.hdr_len <= l.pos && l.instr <= l.pos - l.hdr_len
+                     && end <= 0xffffffffull
+                     && (i + 1 == n || end <= lits[i + 1].pos);
+        if (!ok)
+        {
+            // (a pair out of order is reported at its second literal)
+            const bool self = l.hdr_len > l.pos || l.instr > l.pos - l.hdr_len
+                           || end > 0xffffffffull;
+            if (bad)
+                *bad = self ? i : i + 1;
+            return QHUFF_EINVAL;
+        }
+    }
+    return QHUFF_OK;
 }

@@ -932,6 +932,52 @@ qhuff_decode_stream(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
     return finish_launch(c, st);
 }
 
+// ---- literals in place (qhuff_wire.hip) ------------------------------------
+
+extern "C" int
+qhuff_decode_wire(qhuff_ctx *c, const uint8_t *buf,
+                  const struct qhuff_literal *lits, uint32_t n,
+                  uint32_t max_len, uint8_t *out, uint32_t *out_off,
+                  uint8_t *status, void *stream)
+{
+    if (!c || !out_off || (n && (!buf || !lits || !out || !status)))
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    const uint64_t ts = decode_tile_strings();
+    const uint64_t tiles = (n + ts - 1) / ts;
+    int rc = prepare_launch(c, tiles, st);
+    if (rc)
+        return rc;
+    WireArgs a;
+    a.d.in = buf;
+    // (the tile pipeline's offsets pointer: the policy reads descriptors)
+    a.d.in_off = (const uint32_t *) lits;
+    a.d.out = out;
+    a.d.out_off = out_off;
+    a.d.status = status;
+    a.d.win = c->tab->win;
+    a.d.sorted = c->tab->sorted;
+    a.d.long2 = c->tab->long2;
+    a.d.n = n;
+    a.d.c = coord(c, tiles);
+    a.d.lp = c->lp;
+    a.max_len = max_len;
+    // (the decode kernels' resident grid, as qhuff_decode_stream)
+    const uint64_t wpb = (uint64_t) wire_waves_per_block();
+    const uint32_t grid = grid_for(c, tiles, wpb, c->dec_grid, &a.d.c.spread);
+    hipEvent_t e0, e1;
+    const uint32_t slot = timing_slot(c, QHUFF_KIND_DECODE, &e0, &e1);
+    HIPCHK(c, launch_wire(a, grid, st, e0, e1));
+    timing_commit(c, slot, QHUFF_KIND_DECODE);
+    return finish_launch(c, st);
+}
+
 // ---- host helpers --------------------------------------------------------------
 
 extern "C" uint64_t

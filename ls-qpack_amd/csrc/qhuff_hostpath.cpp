@@ -828,6 +828,77 @@ qhuff_decode_literals_ex(qhuff_ctx *c, const uint8_t *buf,
     return QHUFF_OK;
 }
 
+// The literals decoded where they lie (qhuff_decode_wire): the wire bytes
+// from the first literal's instruction to the last literal's end go up as
+// they are, with the descriptors; one launch; exactly the decoded bytes
+// come back.  No payload is gathered and no result interleaved on the host.
+// Stage layout: [16 | wire bytes | 16 | lits | out_off | status | out]; the
+// kernel sees the caller's positions: `buf` rebased by -lo.
+extern "C" int
+qhuff_decode_wire_host(qhuff_ctx *c, const uint8_t *buf,
+                       const struct qhuff_literal *lits, uint32_t n,
+                       uint32_t max_len, uint8_t *out, uint32_t *out_off,
+                       uint8_t *status)
+{
+    if (!c || !out_off || (n && (!buf || !lits || !out || !status)))
+        return QHUFF_EINVAL;
+    if (n == 0)
+    {
+        out_off[0] = 0;
+        return QHUFF_OK;
+    }
+    if (qhuff_literals_check(lits, n, nullptr))
+        return QHUFF_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the order rule puts every payload behind the first literal's
+    // instruction; an instruction the limit may read (a VALUE literal's) is
+    // the one thing it lets lie before that
+    uint64_t lo = lits[0].instr < lits[0].pos ? lits[0].instr : lits[0].pos;
+    if (max_len)
+        for (uint32_t i = 1; i < n; ++i)
+            if (lits[i].instr < lo)
+                lo = lits[i].instr;
+    const uint64_t hi = (uint64_t) lits[n - 1].pos + lits[n - 1].len;
+    const uint64_t span = hi - lo, bound = qhuff_literals_bound(lits, n);
+    if (bound > 0xffffffffull || span > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const size_t o_buf = 16, o_lits = up16(o_buf + span) + 16;
+    const size_t o_oo = o_lits + 16ull * n;
+    const size_t o_st = o_oo + up16(4ull * (n + 1));
+    const size_t o_out = o_st + up16(n);
+    int rc = ensure_stage(c, o_out + up16(bound));
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t sk = c->own_stream;
+    memcpy(H + o_buf, buf + lo, span);
+    memcpy(H + o_lits, lits, 16ull * n);
+    HIPCHK(c, hipMemcpyAsync(D, H, o_oo, hipMemcpyHostToDevice, sk));
+    rc = qhuff_decode_wire(c, D + o_buf - lo,
+                           (const struct qhuff_literal *) (D + o_lits), n,
+                           max_len, D + o_out, (uint32_t *) (D + o_oo),
+                           D + o_st, sk);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(H + o_oo, D + o_oo, o_out - o_oo,
+                             hipMemcpyDeviceToHost, sk));
+    HIPCHK(c, hipStreamSynchronize(sk));
+    rc = mirror_error(c);
+    if (rc)
+        return rc;
+    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
+    if (total)
+    {
+        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
+                                 hipMemcpyDeviceToHost, sk));
+        HIPCHK(c, hipStreamSynchronize(sk));
+        memcpy(out, H + o_out, total);
+    }
+    memcpy(out_off, H + o_oo, 4ull * (n + 1));
+    memcpy(status, H + o_st, n);
+    return QHUFF_OK;
+}
+
 // ---- header hashing, host buffers ----------------------------------------------
 
 // Stage layout: [name/value bytes | offsets (2n + 1) | name_hash | nameval_hash].

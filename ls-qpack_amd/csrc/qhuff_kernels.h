@@ -54,6 +54,18 @@ struct StreamArgs
     const uint8_t *flags;        // n, or null: no chunk is final
 };
 
+// literals decoded in place from wire data (qhuff_wire.hip): the decode
+// arguments -- d.in the wire buffer, d.in_off the n 16-byte descriptors
+// (struct qhuff_literal) reinterpreted -- and the length limit.  (The static
+// table's name lengths, qhuff_names.h, are a constant of the kernel's code
+// object, kWireNames in qhuff_wire_impl.h: no pointer to carry and nothing
+// to upload.)
+struct WireArgs
+{
+    DecArgs d;
+    uint32_t max_len;            // 0: no limit
+};
+
 struct HashArgs
 {
     const uint8_t *in;
@@ -169,6 +181,10 @@ hipError_t launch_stream(const StreamArgs &a, uint32_t grid, hipStream_t st,
                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t stream_occupancy(int *blocks_per_cu);
 int stream_waves_per_block();
+hipError_t launch_wire(const WireArgs &a, uint32_t grid, hipStream_t st,
+                       hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t wire_occupancy(int *blocks_per_cu);
+int wire_waves_per_block();
 hipError_t launch_hash(const HashArgs &a, uint32_t max_grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t hash_occupancy(int *blocks_per_cu);

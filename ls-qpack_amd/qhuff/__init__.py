@@ -44,6 +44,7 @@ EXPORTS = (
     "qhuff_decode_batch_multi", "qhuff_host_register", "qhuff_host_unregister",
     "qhuff_decode_stream_bound", "qhuff_decode_stream",
     "qhuff_decode_stream_host",
+    "qhuff_literals_check", "qhuff_decode_wire", "qhuff_decode_wire_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -254,6 +255,15 @@ def lib():
         L.qhuff_decode_stream_host.restype = C.c_int
         L.qhuff_decode_stream_host.argtypes = [vp, vp, u32p, C.c_uint32, vp,
                                                vp, vp, u32p, vp]
+        L.qhuff_literals_check.restype = C.c_int
+        L.qhuff_literals_check.argtypes = [vp, C.c_uint32,
+                                           C.POINTER(C.c_uint32)]
+        L.qhuff_decode_wire.restype = C.c_int
+        L.qhuff_decode_wire.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32,
+                                        vp, u32p, vp, vp]
+        L.qhuff_decode_wire_host.restype = C.c_int
+        L.qhuff_decode_wire_host.argtypes = [vp, vp, vp, C.c_uint32,
+                                             C.c_uint32, vp, u32p, vp]
         _lib = L
     return _lib
 
@@ -321,6 +331,37 @@ def scan_encoder_stream(buf, pos_base=0):
     rc, lits = _scan(lib().qhuff_scan_encoder_stream, bytes(buf), pos_base,
                      C.byref(consumed))
     return rc, lits, consumed.value
+
+
+def literals_array(lits):
+    """[Literal] -> the descriptors as qhuff_decode_wire reads them: a numpy
+    uint8 array of 16 * n bytes (torch.from_numpy(...).cuda() for the device
+    call)."""
+    import numpy as np
+    n = len(lits)
+    arr = (Literal * max(n, 1))(*lits)
+    return np.frombuffer(bytes(arr), dtype=np.uint8)[:16 * n].copy()
+
+
+def literals_check(lits):
+    """qhuff_literals_check: the order rule of decode_wire over [Literal] (or
+    their uint8 array) -> (rc, first offending index or None)."""
+    import numpy as np
+    a = lits if isinstance(lits, np.ndarray) else literals_array(lits)
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    bad = C.c_uint32(0xffffffff)
+    rc = lib().qhuff_literals_check(_np_ptr(a) if len(a) else None,
+                                    len(a) // 16, C.byref(bad))
+    return rc, (bad.value if rc != OK else None)
+
+
+def literals_bound(lits):
+    """qhuff_literals_bound over [Literal] or their uint8 array"""
+    import numpy as np
+    a = lits if isinstance(lits, np.ndarray) else literals_array(lits)
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    return int(lib().qhuff_literals_bound(_np_ptr(a) if len(a) else None,
+                                          len(a) // 16))
 
 
 def dec_int(buf, prefix_bits):
@@ -775,6 +816,53 @@ class Codec:
                 self._ctx, _np_ptr(src), arr, n, max_len, _np_ptr(out),
                 _np_ptr(out_off), _np_ptr(status))
         self._check(rc, "qhuff_decode_literals_host")
+        return ([out[out_off[i]:out_off[i + 1]].tobytes() for i in range(n)],
+                status[:n])
+
+    # literals decoded in place from wire data ------------------------------
+    def decode_wire_into(self, buf, lits, n, max_len, out, out_off, status,
+                         stream=None):
+        """qhuff_decode_wire: buf the wire bytes, lits the n descriptors (16
+        bytes each), all device tensors; the descriptors must satisfy the
+        order rule (literals_check)."""
+        rc = lib().qhuff_decode_wire(
+            self._ctx, buf.data_ptr(), lits.data_ptr(), n, max_len or 0,
+            out.data_ptr(), out_off.data_ptr(), status.data_ptr(),
+            self._stream(stream))
+        self._check(rc, "qhuff_decode_wire")
+
+    def decode_wire(self, buf, lits, max_len=None, stream=None, bound=None):
+        """buf: uint8 cuda tensor of wire bytes; lits: uint8 cuda tensor of
+        16 * n bytes (literals_array of the scanners' Literals).  Returns
+        (out uint8 [bound], out_off int32 [n+1], status uint8 [n]).  bound:
+        qhuff_literals_bound of the descriptors when the caller has it (it
+        is computed from a host copy of lits otherwise)."""
+        import torch
+        n = lits.numel() // 16
+        if bound is None:
+            bound = literals_bound(lits.cpu().numpy())
+        out = torch.empty(bound, dtype=torch.uint8, device=buf.device)
+        out_off = torch.empty(n + 1, dtype=torch.int32, device=buf.device)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=buf.device)
+        self.decode_wire_into(buf, lits, n, max_len, out, out_off, status,
+                              stream)
+        return out, out_off, status[:n]
+
+    def decode_wire_host(self, buf, lits, max_len=None):
+        """qhuff_decode_wire_host over host buffer buf and [Literal] ->
+        (list of bytes, status uint8 ndarray), as decode_literals_host."""
+        import numpy as np
+        n = len(lits)
+        arr = (Literal * max(n, 1))(*lits)
+        src = np.frombuffer(bytes(buf) + b"\0", dtype=np.uint8)
+        cap = int(lib().qhuff_literals_bound(arr, n))
+        out = np.zeros(cap, dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint32)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = lib().qhuff_decode_wire_host(
+            self._ctx, _np_ptr(src), arr, n, max_len or 0, _np_ptr(out),
+            _np_ptr(out_off), _np_ptr(status))
+        self._check(rc, "qhuff_decode_wire_host")
         return ([out[out_off[i]:out_off[i + 1]].tobytes() for i in range(n)],
                 status[:n])
 
