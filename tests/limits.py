@@ -1,0 +1,651 @@
+"""Inputs that sit exactly on the limits of the kernels' LDS layouts, and a
+plain-Python restatement of the path each 64-string tile takes (no GPU).
+
+Every kernel places per-string data in LDS by worst-case arithmetic -- a
+Huffman string of len bytes decodes to at most floor(8 * len / 5) bytes,
+reached only by strings made of 5-bit codes -- and chooses its path by exact
+comparisons.  The builders here make strings that reach those worst cases
+(each asserts its own claim with the oracle); classify() / classify_enc()
+say which side of every comparison a tile is on, from the constants of the
+headers written out as numbers; DECODE and ENCODE name one tile per edge
+and side.
+tests/test_limits.py checks the fixtures against the model (CPU) and the
+kernels against the oracle on them (GPU); the wire, stream, service and
+shim tests take the same strings through their entry points.
+"""
+import random
+
+import numpy as np
+
+import _paths  # noqa: F401
+import oracle_lib as O
+from test_coop_model import coop_model, seg_bits  # noqa: F401
+
+# ---- the headers' constants, as numbers --------------------------------------
+
+TS = 64                       # kWT / kDecTS (qhuff_device.h): strings per tile
+STAGE = 3072                  # kStageCap = kDecInCap = kEncInCap (qhuff_pipeline.h)
+OUT_CAP = 3072                # kDecStageCap / kEncOutCap: P::kOutCap
+OUT_FREE = 64                 # `total + 64 <= kOutCap` (tile_pipeline)
+OUT_FAST = 3008               # the largest fast output: kOutCap - 64
+BIG_SLOT = 12288              # kBigSlotBytes (qhuff_device.h)
+FIX_STRIDE = 108              # kFixStride (qhuff_decode_impl.h)
+FIX_MAX = 66                  # kFixMaxLen = 5 * (kFixStride - 1) / 8
+STREAM_FIX_MAX = 65           # kStreamFixMaxLen = 5 * (kFixStride - 3) / 8
+COOP_MIN = 128                # kCoopMin (qhuff_decode_impl.h)
+COOP_MAX_STRINGS = 48         # `popcount(coop) > 48` (codec_range)
+VAR_ARENA = 2 * TS + 8 * STAGE // 5 + 16      # kVarArenaBytes = 5059
+COPY_MIN = 64                 # `ls > 64` (dec_big_sizes put): copy_out
+# (kDenseWords = kStageCap / 4 + 4 = 772, two of them spare: the largest
+# dense tile has 24576 code bits, all of a 3072-byte stage at 8 bits a byte)
+DENSE_BITS = 32 * (STAGE // 4 + 4 - 2)        # kDenseBits = 24640
+DENSE_FREE = 64               # `se + 64 <= kDenseBits` (EncPolicyT::codec_range)
+DENSE_MAX = 24576             # the largest dense tile: kDenseBits - 64
+ENC_COOP_BITS = 1024          # kEncCoopBits (qhuff_encode_impl.h)
+
+assert FIX_MAX == 5 * (FIX_STRIDE - 1) // 8
+assert STREAM_FIX_MAX == 5 * (FIX_STRIDE - 3) // 8
+assert OUT_FAST == OUT_CAP - OUT_FREE and DENSE_MAX == DENSE_BITS - DENSE_FREE
+
+# ---- builders --------------------------------------------------------------------
+
+CODE_LEN = [O.code_of(s)[1] for s in range(256)]
+F5 = bytes(s for s in range(256) if CODE_LEN[s] == 5)
+assert F5 == b"012aceiost"
+B30 = bytes(s for s in range(256) if CODE_LEN[s] == 30)
+assert B30 == bytes([10, 13, 22])
+BY_LEN = {}
+for _s in range(256):
+    BY_LEN.setdefault(CODE_LEN[_s], []).append(_s)
+
+TOKEN = b"abcdefghijklmnopqrstuvwxyz0123456789-_./:;=, "
+
+
+def code_bits(s):
+    return sum(CODE_LEN[c] for c in s)
+
+
+def _checked(s, L):
+    h = O.huffman_enc(s)
+    assert len(h) == L, (len(h), L)
+    st, out = O.huff_decode(h)
+    assert st == O.OK and out == s
+    return h
+
+
+def maxexp(L, rng):
+    """A Huffman string of exactly L bytes that decodes to floor(8 * L / 5)
+    bytes, the most any string of L bytes can: random 5-bit symbols.  (5 *
+    floor(8L / 5) > 8L - 5, so the padding is at most 4 bits: every L.)"""
+    return _checked(bytes(rng.choice(F5) for _ in range(8 * L // 5)), L)
+
+
+def periodic(L, unit):
+    """maxexp(L) with `unit` (5-bit symbols) repeated: every segment of the
+    cooperative decode looks alike, so a guessed walk that starts off a
+    code boundary never meets the true one."""
+    assert unit and all(c in F5 for c in unit)
+    n = 8 * L // 5
+    return _checked((unit * (n // len(unit) + 1))[:n], L)
+
+
+def symbols(k, rng):
+    """k random 5-bit symbols: ceil(5k / 8) input bytes, k output bytes."""
+    return _checked(bytes(rng.choice(F5) for _ in range(k)), (5 * k + 7) // 8)
+
+
+def invalid_twin(h):
+    """h (valid) with its last padding bit cleared -- or, where it has no
+    padding, one 0x00 byte appended (five bits of '0' and three zero padding
+    bits): rejected by the oracle only after every symbol of h has been
+    decoded."""
+    st, out = O.huff_decode(h)
+    assert st == O.OK
+    pad = 8 * len(h) - code_bits(out)
+    assert 0 <= pad < 8
+    t = h[:-1] + bytes([h[-1] & 0xfe]) if pad else h + b"\x00"
+    assert O.huff_decode(t)[0] == O.ERROR
+    pre, eos = O.decoded_prefix(t)
+    assert not eos and pre == (out if pad else out + b"0")
+    return t
+
+
+def with_bits(n, bits, rng):
+    """n bytes whose codes total exactly `bits` bits: as few 30-bit symbols
+    as it takes, the rest of 5..8 bits, in random order (the encoder's
+    edges are counted in code bits)."""
+    for n30 in range(n + 1):
+        m, r = n - n30, bits - 30 * n30
+        if 5 * m <= r <= 8 * m:
+            break
+    else:
+        raise ValueError("no %d symbols of %d bits" % (n, bits))
+    lens = [5] * m
+    for i in range(r - 5 * m):
+        lens[i % m] += 1
+    lens += [30] * n30
+    rng.shuffle(lens)
+    s = bytes(rng.choice(BY_LEN[x]) for x in lens)
+    assert len(s) == n and code_bits(s) == bits
+    return s
+
+
+def token_tiles(rng, tiles=2):
+    """ordinary tiles (Huffman strings of 8..40 token characters)"""
+    return [O.huffman_enc(bytes(rng.choice(TOKEN)
+                                for _ in range(rng.randint(8, 40))))
+            for _ in range(TS * tiles)]
+
+
+def token_raw(rng, tiles=2):
+    return [bytes(rng.choice(TOKEN) for _ in range(rng.randint(8, 40)))
+            for _ in range(TS * tiles)]
+
+
+def place(rng, tile, residue, around=token_tiles):
+    """two ordinary tiles, `tile`, two ordinary tiles, and the bytes of
+    padding in front that put the tile's first byte on `residue` (mod 16)
+    of a 16-byte-aligned buffer: (strings, pad_front, index of the tile)"""
+    pre, post = around(rng), around(rng)
+    pad = (residue - sum(len(s) for s in pre)) % 16
+    return pre + list(tile) + post, pad, len(pre) // TS
+
+
+def pack(strings):
+    off = np.zeros(len(strings) + 1, dtype=np.uint32)
+    np.cumsum([len(s) for s in strings], out=off[1:])
+    return np.frombuffer(b"".join(strings), dtype=np.uint8).copy(), off
+
+
+# ---- the layout model --------------------------------------------------------------
+
+def _span(res, a, b):
+    """16-byte-aligned span of the bytes [a, b) of a buffer at `res` mod 16
+    (tile_span, unit_len)"""
+    return ((res + b + 15) & ~15) - ((res + a) & ~15)
+
+
+def _unit(off, sizes, lo, hi, t0):
+    """codec_range over the lanes [lo, hi) of the tile at string t0: the
+    arena, the cooperative set and the last slot's end"""
+    hl = [int(off[t0 + i + 1]) - int(off[t0 + i]) for i in range(lo, hi)]
+    fixed = all(x <= FIX_MAX for x in hl)
+    A = int(off[t0 + lo])
+    coop = [] if fixed else [lo + i for i, x in enumerate(hl) if x > COOP_MIN]
+    if len(coop) > COOP_MAX_STRINGS:         # (unreachable: see classify)
+        coop = []
+    u = {"lo": lo, "hi": hi, "lone": False,
+         "arena": "fixed" if fixed else "var", "coop": coop,
+         "out": sum(sizes[t0 + lo:t0 + hi])}
+    if coop:
+        S = seg_bits([hl[i - lo] for i in coop])
+        u["S"] = S
+        u["segs"] = [max(1, 8 * hl[i - lo] // S) for i in coop]
+        assert sum(u["segs"]) <= 64
+    # the bytes the last lane may write: its bound and the emitter's two
+    last = hi - 1
+    if fixed:
+        u["slot_end"] = FIX_STRIDE * last + 8 * hl[-1] // 5 + 2
+        u["arena_cap"] = FIX_STRIDE * TS
+    else:
+        u["slot_end"] = (2 * last + 8 * (int(off[t0 + last]) - A) // 5
+                         + 8 * hl[-1] // 5 + 2)
+        u["arena_cap"] = VAR_ARENA
+    return u
+
+
+def classify(off, base_residue, oracle_sizes):
+    """The path of every 64-string tile of a decode batch through the full
+    kernel (tile_pipeline, DecPolicyT::codec_range, dec_big_sizes): off the
+    n + 1 offsets as the kernel gets them, base_residue the data pointer
+    mod 16, oracle_sizes the n output sizes (0 for a rejected string).  Per
+    tile a dict:
+
+      staged   the 16-byte-aligned span of its input is <= 3072
+      units    one entry for a staged tile; for an unstaged one the greedy
+               runs of lanes whose aligned span is <= 3072, and a string
+               past that alone ("lone": walked in global memory, with its
+               bound 8 * len / 5 + 1 and the output before it, "run"); each
+               with its arena ("fixed": every string <= 66 bytes, "var"),
+               its cooperative lanes (> 128 bytes), their segment size S and
+               segments, its output bytes and the end of its last slot
+               against the arena
+      total    output bytes
+      path     "fast" (staged, no cooperative string, total <= 3008),
+               "slot" (all of it fits the 12288-byte slot as it is
+               produced), "slow"
+      copy_out the lanes whose bytes leave the arena through copy_out
+               (more than 64 of them) rather than the byte loop, in a tile
+               that goes to a slot
+
+    A unit holds at most floor(3072 / 129) = 23 strings above kCoopMin, so
+    the `popcount(coop) > 48` branch of codec_range cannot be reached while
+    kDecInCap is 3072; no fixture is built for it."""
+    off = [int(x) for x in off]
+    sizes = [int(x) for x in oracle_sizes]
+    n = len(off) - 1
+    res = base_residue
+    tiles = []
+    for t0 in range(0, n, TS):
+        cnt = min(TS, n - t0)
+        o = off[t0:t0 + cnt + 1]
+        total = sum(sizes[t0:t0 + cnt])
+        info = {"staged": _span(res, o[0], o[cnt]) <= STAGE, "total": total,
+                "copy_out": []}
+        if info["staged"]:
+            u = _unit(off, sizes, 0, cnt, t0)
+            info["units"] = [u]
+            if not u["coop"] and total <= OUT_FAST:
+                info["path"] = "fast"
+            else:
+                info["path"] = "slot" if total <= BIG_SLOT else "slow"
+        else:
+            units, run, fits, i0 = [], 0, True, 0
+            while i0 < cnt:
+                k = sum(1 for i in range(i0, cnt)
+                        if _span(res, o[i0], o[i + 1]) <= STAGE)
+                if k == 0:
+                    bound = 8 * (o[i0 + 1] - o[i0]) // 5 + 1
+                    fits = fits and run + bound <= BIG_SLOT
+                    units.append({"lo": i0, "hi": i0 + 1, "lone": True,
+                                  "bound": bound, "run": run, "coop": [],
+                                  "into_slot": fits, "out": sizes[t0 + i0]})
+                    run += sizes[t0 + i0]
+                    i0 += 1
+                    continue
+                u = _unit(off, sizes, i0, i0 + k, t0)
+                u["run"] = run
+                fits = fits and run + u["out"] <= BIG_SLOT
+                run += u["out"]
+                units.append(u)
+                i0 += k
+            info["units"] = units
+            info["path"] = "slot" if fits else "slow"
+        if info["path"] == "slot":
+            info["copy_out"] = [i for u in info["units"] if not u["lone"]
+                                for i in range(u["lo"], u["hi"])
+                                if sizes[t0 + i] > COPY_MIN]
+        tiles.append(info)
+    return tiles
+
+
+def classify_enc(data, off, base_residue, mode, oracle_sizes):
+    """The same for an encode batch (EncPolicyT::codec_range / emit,
+    enc_big_sizes): data the whole input buffer, off the n + 1 offsets into
+    it.  Per tile: staged; se, the code bits of the span's bytes up to the
+    tile's end (the dense pass codes the span from its 16-byte boundary, so
+    the bytes in front of the tile count), and dense = se <= 24576, whatever
+    a string then emits -- a literal that falls back to raw counts its code
+    bits all the same; total; path as classify; coop, the lanes whose
+    Huffman payload is copied by the whole wave (more than 1024 bits, in a
+    dense tile or unit that is emitted from the out stage)."""
+    off = [int(x) for x in off]
+    sizes = [int(x) for x in oracle_sizes]
+    raw = bytes(data)
+    n = len(off) - 1
+    res = base_residue
+    tiles = []
+
+    def unit(lo, hi, t0):
+        a, b = off[t0 + lo], off[t0 + hi]
+        lead = (res + a) % 16
+        se = code_bits(raw[a - lead:b]) if a >= lead else None
+        bits = [code_bits(raw[off[t0 + i]:off[t0 + i + 1]])
+                for i in range(lo, hi)]
+        ln = [off[t0 + i + 1] - off[t0 + i] for i in range(lo, hi)]
+        huff = [mode == 0 or (x + 7) // 8 < l for x, l in zip(bits, ln)]
+        out = sum(sizes[t0 + lo:t0 + hi])
+        dense = se is not None and se <= DENSE_MAX
+        emitted = dense and out <= OUT_FAST
+        return {"lo": lo, "hi": hi, "lone": False, "se": se, "dense": dense,
+                "out": out,
+                "coop": [lo + i for i in range(hi - lo)
+                         if emitted and huff[i] and sizes[t0 + lo + i]
+                         and bits[i] > ENC_COOP_BITS]}
+
+    for t0 in range(0, n, TS):
+        cnt = min(TS, n - t0)
+        o = off[t0:t0 + cnt + 1]
+        total = sum(sizes[t0:t0 + cnt])
+        info = {"staged": _span(res, o[0], o[cnt]) <= STAGE, "total": total}
+        if info["staged"]:
+            u = unit(0, cnt, t0)
+            info["units"] = [u]
+            info["se"], info["dense"] = u["se"], u["dense"]
+            if total <= OUT_FAST:
+                info["path"] = "fast"
+            else:
+                info["path"] = "slot" if total <= BIG_SLOT else "slow"
+                u["coop"] = []               # (packed by each lane)
+            info["coop"] = u["coop"]
+        else:
+            units, run, fits, i0 = [], 0, True, 0
+            while i0 < cnt:
+                k = sum(1 for i in range(i0, cnt)
+                        if _span(res, o[i0], o[i + 1]) <= STAGE)
+                if k == 0:
+                    fits = fits and run + sizes[t0 + i0] <= BIG_SLOT
+                    units.append({"lo": i0, "hi": i0 + 1, "lone": True,
+                                  "run": run, "out": sizes[t0 + i0],
+                                  "coop": []})
+                    run += sizes[t0 + i0]
+                    i0 += 1
+                    continue
+                u = unit(i0, i0 + k, t0)
+                u["run"] = run
+                fits = fits and run + u["out"] <= BIG_SLOT
+                run += u["out"]
+                units.append(u)
+                i0 += k
+            info["units"] = units
+            info["path"] = "slot" if fits else "slow"
+            info["coop"] = [i for u in units for i in u["coop"]]
+        tiles.append(info)
+    return tiles
+
+
+# ---- the fixtures ------------------------------------------------------------------
+
+class Fixture:
+    """One special tile: `tile` its 64 strings (Huffman strings for decode,
+    raw ones for encode), `residues` the alignments (mod 16) of its first
+    byte it is run at, `key` the property of its classify() entry it is
+    named for and `want` that property's value per residue; `twin` the
+    fixture on the other side of the edge; `special` the lanes of the
+    strings the fixture is about."""
+
+    def __init__(self, name, tile, key, want, edge, residues=(0, 5),
+                 twin=None, special=(), mode=None):
+        assert len(tile) == TS
+        self.name, self.tile, self.key, self.edge = name, tile, key, edge
+        self.want = want if isinstance(want, dict) else {
+            r: want for r in residues}
+        self.residues, self.twin, self.special = residues, twin, special
+        self.mode = mode
+
+    def __repr__(self):
+        return self.name
+
+
+def k_arena(i):
+    return i["units"][0]["arena"]
+
+
+def k_path(i):
+    return i["path"]
+
+
+def k_staged_path(i):
+    return (i["staged"], i["path"])
+
+
+def k_coop(i):
+    return tuple(c for u in i["units"] for c in u["coop"])
+
+
+def k_copy(i):
+    return tuple(i["copy_out"])
+
+
+def k_segs(i):
+    return tuple((u.get("S"), tuple(u.get("segs", ()))) for u in i["units"]
+                 if u["coop"])
+
+
+def k_dense(i):
+    return i["dense"]
+
+
+def k_enc_coop(i):
+    return tuple(i["coop"])
+
+
+def _decode_fixtures():
+    rng = random.Random(20240)
+    fx = []
+
+    def add(*a, **k):
+        fx.append(Fixture(*a, **k))
+
+    # hl > kFixMaxLen
+    t66 = [maxexp(66, rng) for _ in range(20)] + [maxexp(10, rng)
+                                                  for _ in range(44)]
+    rng.shuffle(t66)
+    sp66 = tuple(i for i, h in enumerate(t66) if len(h) == 66)
+    t67 = list(t66)
+    t67[sp66[7]] = maxexp(67, rng)
+    add("fix66", t66, k_arena, "fixed", "hl > kFixMaxLen, at it: 20 strings "
+        "of 66 bytes fill 105 + 2 bytes of their 108-byte stride",
+        twin="var67", special=sp66)
+    add("var67", t67, k_arena, "var", "hl > kFixMaxLen, past it: one string "
+        "of 67 bytes puts the tile in the variable arena", twin="fix66",
+        special=sp66)
+    # total + 64 <= kOutCap
+    t3008 = [symbols(47, rng) for _ in range(64)]
+    t3009 = list(t3008)
+    t3009[41] = symbols(48, rng)
+    add("out3008", t3008, k_path, "fast", "total + 64 <= kOutCap, at it: "
+        "output 3008", twin="out3009")
+    add("out3009", t3009, k_path, "slot", "total + 64 <= kOutCap, past it: "
+        "output 3009 leaves the arena for a big slot", twin="out3008")
+    # the variable arena packed to its top
+    full = [maxexp(48, rng) for _ in range(62)] + [maxexp(67, rng),
+                                                   maxexp(29, rng)]
+    add("arena_full", full, k_staged_path,
+        {0: (True, "slot"), 5: (False, "slot")},
+        "span <= kDecInCap, exactly 3072 at residue 0: the variable arena "
+        "packed to its top; at residue 5 the span is 3088 and the tile "
+        "splits into units", special=tuple(range(0, 64, 1)))
+    # ls > 64
+    t64 = [symbols(64 + (i & 1), rng) for i in range(64)]
+    add("copy64_65", t64, k_copy, tuple(range(1, 64, 2)),
+        "ls > 64 in put: the 64-byte outputs by the byte loop, the 65-byte "
+        "ones by copy_out, alternating")
+    # hl > kCoopMin
+    sh = [maxexp(rng.randint(1, 40), rng) for _ in range(61)]
+    c128 = sh[:30] + [maxexp(128, rng), maxexp(127, rng), maxexp(70, rng)] \
+        + sh[30:]
+    c129 = sh[:30] + [maxexp(128, rng), maxexp(129, rng), maxexp(200, rng)] \
+        + sh[30:]
+    add("coop128", c128, k_coop, (), "hl > kCoopMin, at it: a string of 128 "
+        "bytes is decoded by its lane", twin="coop129", special=(30, 31, 32))
+    add("coop129", c129, k_coop, (31, 32), "hl > kCoopMin, past it: 129 and "
+        "200 bytes go to the whole wave (200: N == 8 * len / 5 exactly, "
+        "bitmap inside a full slot), 128 beside them does not",
+        twin="coop128", special=(31, 32, 30))
+    # 23 cooperative strings, one segment each
+    c23 = [maxexp(129, rng) for _ in range(23)] \
+        + [maxexp(3, rng) for _ in range(23)] \
+        + [maxexp(2, rng) for _ in range(18)]
+    rng.shuffle(c23)
+    sp23 = tuple(i for i, h in enumerate(c23) if len(h) == 129)
+    add("coop23", c23, k_segs, {0: ((608, (1,) * 23),)},
+        "the most cooperative strings a 3072-byte stage holds: 23, S = 608, "
+        "one segment each", residues=(0,), special=sp23)
+    # 63 segments, >= 60 rounds of B
+    for L in (504, 3024):
+        for tag, mk in (("ssi", lambda L=L: periodic(L, b"ssi")),
+                        ("0", lambda L=L: periodic(L, b"0")),
+                        ("rand", lambda L=L: maxexp(L, rng))):
+            for lane in (0, 29, 63):
+                room = 3072 - 16 - L         # (any residue: one chunk spare)
+                sh = [b""] * 63
+                for i in rng.sample(range(63), 12):
+                    sh[i] = maxexp(min(room // 12, rng.randint(1, 30)), rng)
+                tile = sh[:lane] + [mk()] + sh[lane:]
+                add("coop63_%d_%s_lane%d" % (L, tag, lane), tile, k_segs,
+                    ((8 * L // 63, (63,)),),
+                    "one string in 63 segments (8L = 63 S): %s" %
+                    ("a periodic one, >= 60 rounds of B" if tag != "rand"
+                     else "a random one, <= 4 rounds"),
+                    residues=(0, 11), special=(lane,))
+    # several round chains in one wave
+    for k in (2, 3, 8):
+        tile = [b""] * 64
+        lanes = sorted(rng.sample(range(64), k))
+        for i in lanes:
+            tile[i] = periodic(3000 // k, b"ssc")
+        rest = [i for i in range(64) if i not in lanes]
+        for i in rng.sample(rest, 14):
+            tile[i] = maxexp(rng.randint(1, 4), rng)
+        add("coop_k%d" % k, tile, k_coop, tuple(lanes),
+            "%d equal periodic strings of %d bytes: several round chains in "
+            "one wave" % (k, 3000 // k), residues=(0, 3),
+            special=tuple(lanes))
+    # run + ut <= kBigSlotBytes
+    s88 = [symbols(192, rng) for _ in range(64)]
+    s89 = list(s88)
+    s89[50] = symbols(193, rng)
+    add("slot12288", s88, k_staged_path, (False, "slot"),
+        "run + ut <= kBigSlotBytes, at it: units whose output totals 12288",
+        twin="slot12289", special=tuple(range(64)))
+    add("slot12289", s89, k_staged_path, (False, "slow"),
+        "run + ut <= kBigSlotBytes, past it: 12289, a slow tile",
+        twin="slot12288")
+    # run + bound <= kBigSlotBytes, a string walked in global memory
+    one = symbols(1, rng)
+    g79, g80 = maxexp(7679, rng), maxexp(7680, rng)
+    add("glob7679_lane0", [g79, one, one] + [b""] * 61, k_path, "slot",
+        "run + bound <= kBigSlotBytes, below it: bound 12287 at run 0, and "
+        "the two bytes after it fill the slot", twin="glob7680_lane0",
+        special=(0,))
+    add("glob7680_lane0", [g80, one, one] + [b""] * 61, k_path, "slow",
+        "run + bound <= kBigSlotBytes, past it: bound 12289, counted then "
+        "slow", twin="glob7679_lane0", special=(0,))
+    add("glob7679_lane63_run1", [b""] * 30 + [one] + [b""] * 32 + [g79],
+        k_path, "slot", "run + bound <= kBigSlotBytes, at it: run 1 + "
+        "bound 12287", twin="glob7679_lane63_run2", special=(63,))
+    add("glob7679_lane63_run2", [one] + [b""] * 29 + [one] + [b""] * 32
+        + [g79], k_path, "slow", "run + bound <= kBigSlotBytes, past it: "
+        "run 2 + bound 12287", twin="glob7679_lane63_run1", special=(63,))
+    byname = {f.name: f for f in fx}
+    # a rejected string that decoded all its symbols first
+    for name in ("fix66", "arena_full", "coop129", "coop63_504_ssi_lane29",
+                 "coop63_3024_0_lane63", "slot12288"):
+        f = byname[name]
+        tile = list(f.tile)
+        for i in f.special[::3]:
+            tile[i] = invalid_twin(tile[i])
+        add(name + "_invalid", tile, None, None, "every third special "
+            "string of %s replaced by its invalid twin: status 1, size 0, "
+            "neighbours untouched" % name, residues=f.residues[:1],
+            special=f.special[::3])
+    return fx
+
+
+def _encode_fixtures():
+    rng = random.Random(20241)
+    fx = []
+
+    def add(*a, **k):
+        fx.append(Fixture(*a, **k))
+
+    def b30(n):
+        return bytes(rng.choice(B30) for _ in range(n))
+    t8 = [b30(12 + (i & 1)) for i in range(64)]
+    t9 = list(t8)
+    t9[20] = t9[20] + bytes([rng.choice(F5)])
+    add("enc_out3008", t8, k_path, "fast", "total + 64 <= kOutCap, at it: "
+        "30-bit codes, 3.75x expansion to 3008 bytes", twin="enc_out3009",
+        residues=(0,), mode=0)
+    add("enc_out3009", t9, k_path, "slot", "total + 64 <= kOutCap, past it: "
+        "3009 bytes", twin="enc_out3008", residues=(0,), mode=0)
+    # se + 64 <= kDenseBits.  40-byte strings of 384 code bits: 48 bytes of
+    # Huffman each, so mode 0 emits 3072 bytes (a big slot) and mode 7 falls
+    # back to raw for every string (41 bytes each, a fast tile) -- and codec()
+    # takes se from the dense offsets before it knows what a string emits,
+    # so the raw strings' codes count: the edge sits inside a fast tile.
+    d76 = [with_bits(40, 384, rng) for _ in range(64)]
+    d77 = d76[:63] + [with_bits(40, 385, rng)]
+    d12 = d76[:63] + [with_bits(40, 384 - 64, rng)]
+    d13 = d76[:63] + [with_bits(40, 385 - 64, rng)]
+    for mode, path in ((0, "slot"), (7, "fast")):
+        add("enc_dense24576_mode%d" % mode, d76, k_dense, True,
+            "se + 64 <= kDenseBits, at it: 24576 code bits (%s tile)" % path,
+            twin="enc_dense24577_mode%d" % mode, residues=(0,), mode=mode)
+        add("enc_dense24577_mode%d" % mode, d77, k_dense, False,
+            "se + 64 <= kDenseBits, past it: 24577 code bits, sized and "
+            "emitted per string", twin="enc_dense24576_mode%d" % mode,
+            residues=(0,), mode=mode)
+        # 24512 + 64 is the stage in bits, 64 below the dense stream's limit
+        add("enc_dense24512_mode%d" % mode, d12, k_dense, True,
+            "24512 code bits: dense", residues=(0,), mode=mode)
+        add("enc_dense24513_mode%d" % mode, d13, k_dense, True,
+            "24513 code bits: dense", residues=(0,), mode=mode)
+    # bits > kEncCoopBits
+    short = [bytes(rng.choice(TOKEN) for _ in range(rng.randint(0, 30)))
+             for _ in range(62)]
+    p1024 = with_bits(204, 1024, rng)
+    assert sorted(CODE_LEN[c] for c in p1024) == [5] * 200 + [6] * 4
+    p1025 = bytes(rng.choice(F5) for _ in range(205))
+    add("enc_coop1024_1025", short[:17] + [p1024] + short[17:40] + [p1025]
+        + short[40:], k_enc_coop, (41,), "bits > kEncCoopBits: the payload "
+        "of 1024 bits by its lane, the one of 1025 by the wave",
+        residues=(0, 5), mode=0, special=(17, 41))
+    # big slot against slow tile
+    s88 = [with_bits(60, 1536, rng) for _ in range(64)]
+    s89 = s88[:33] + [with_bits(60, 1537, rng)] + s88[34:]
+    add("enc_slot12288", s88, k_staged_path, (False, "slot"),
+        "run + ut <= kBigSlotBytes, at it: units packing 12288 bytes",
+        twin="enc_slot12289", residues=(0, 5), mode=0)
+    add("enc_slot12289", s89, k_staged_path, (False, "slow"),
+        "run + ut <= kBigSlotBytes, past it: 12289", twin="enc_slot12288",
+        residues=(0, 5), mode=0)
+    return fx
+
+
+DECODE = _decode_fixtures()
+ENCODE = _encode_fixtures()
+DECODE_BY_NAME = {f.name: f for f in DECODE}
+ENCODE_BY_NAME = {f.name: f for f in ENCODE}
+
+
+def decode_batch_of(f, residue):
+    """(data, off, pad_front, tile index) of fixture f between ordinary
+    tiles: with pad_front bytes in front of data in a 16-byte-aligned
+    buffer (and added to off) the tile's first byte is at `residue`"""
+    rng = random.Random(len(f.name) * 131 + residue)
+    strs, pad, ti = place(rng, f.tile, residue)
+    data, off = pack(strs)
+    assert (int(off[ti * TS]) + pad) % 16 == residue
+    return data, off, pad, ti
+
+
+def encode_batch_of(f, residue):
+    rng = random.Random(len(f.name) * 137 + residue)
+    strs, pad, ti = place(rng, f.tile, residue, around=token_raw)
+    data, off = pack(strs)
+    assert (int(off[ti * TS]) + pad) % 16 == residue
+    return data, off, pad, ti
+
+
+def combined(fixtures, raw=False, repeat=1):
+    """Every fixture at every one of its residues in one batch, two ordinary
+    tiles in front of each (the last ordinary string lengthened to put the
+    fixture's first byte on its residue) and two at the end: a batch of a
+    few hundred tiles, for a grid of fewer waves than that -- every wave
+    then codes several tiles and a fixture's tile is coded between pending
+    ones (repeat: the whole list that many times over).  -> (data, off,
+    [(fixture, residue, tile index)]); the buffer is 16-byte aligned and
+    off[0] is 0."""
+    rng = random.Random(len(fixtures))
+    around = token_raw if raw else token_tiles
+    strs, where, pos = [], [], 0
+    for f in list(fixtures) * repeat:
+        if raw and f.mode != 0:
+            continue
+        for r in f.residues:
+            pre = around(rng)
+            pos += sum(len(s) for s in pre)
+            p = (r - pos) % 16
+            n = len(pre[-1]) + p
+            pre[-1] = bytes(rng.choice(TOKEN) for _ in range(n)) if raw \
+                else maxexp(n, rng)
+            pos += p
+            assert pos % 16 == r and len(strs) % TS == 0
+            where.append((f, r, (len(strs) + len(pre)) // TS))
+            strs += pre + list(f.tile)
+            pos += sum(len(s) for s in f.tile)
+    strs += around(rng)
+    data, off = pack(strs)
+    return data, off, where

@@ -236,3 +236,41 @@ def test_coop_model_invalid_falls_back():
         elif r is not None:
             assert r[0] == out
     assert rejected > 30
+
+
+PERIODIC_L = (504, 1008, 2016, 3024)             # 8 L = 63 S
+
+
+@pytest.mark.parametrize("unit", [b"s", b"0", b"ssi", b"ssc"])
+@pytest.mark.parametrize("L", PERIODIC_L)
+def test_coop_model_periodic(L, unit):
+    """A string of 5-bit codes that repeats a short unit, cut into 63
+    segments (8 L = 63 S): every guessed walk looks like its neighbour's, a
+    walk that starts off a code boundary never meets the true one, and the
+    exact starts travel one segment a round -- 60 rounds or more of B, just
+    below the kernel's guard (++rounds > 64).  The result is the oracle's
+    all the same."""
+    import limits                            # (imports this module)
+    h = limits.periodic(L, unit)
+    S = seg_bits([L])
+    assert 8 * L == 63 * S and max(1, 8 * L // S) == 63
+    r = coop_model(h)
+    assert r is not None
+    st, out = O.huff_decode(h)
+    assert st == O.OK and r[0] == out and len(out) == 8 * L // 5
+    assert 60 <= r[1] <= 64
+
+
+@pytest.mark.parametrize("L", PERIODIC_L)
+def test_coop_model_maxexp_resynchronises(L):
+    """Random strings over the same ten 5-bit symbols, the same lengths and
+    63 segments: the walks meet within a few rounds (what the periodic ones
+    add is the round chain, not the content)."""
+    import limits
+    rng = random.Random(L)
+    for _ in range(8):
+        h = limits.maxexp(L, rng)
+        assert max(1, 8 * L // seg_bits([L])) == 63
+        r = coop_model(h)
+        assert r is not None and r[0] == O.huff_decode(h)[1]
+        assert r[1] <= 4

@@ -138,6 +138,33 @@ def test_decode_invalid_every_dst_len(shim):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("L", [66, 67, 129, 3073])
+def test_decode_full_slot_bad_padding(shim, L):
+    """A string of 5-bit codes that decodes to n = floor(8 L / 5) bytes --
+    all of its arena slot -- with its last padding bit cleared: the
+    keep-rejected replay has all n bytes decoded before the padding error;
+    dst_len n - 1, n and n + 1 end as the reference ends them (L: the fixed arena's limit, one past it, a cooperative
+    string, a string past the stage)."""
+    import limits
+    h = limits.maxexp(L, random.Random(L))
+    n = len(O.huff_decode(h)[1])
+    assert n == 8 * L // 5 and 8 * L - 5 * n > 0
+    enc = limits.invalid_twin(h)
+    assert len(enc) == L
+    assert O.decoded_prefix(enc) == (O.huff_decode(h)[1], False)
+    for dst_len in (n - 1, n, n + 1):
+        got = shim_decode(shim, enc, dst_len)
+        want = oracle_decode(enc, dst_len)
+        assert got == want, (L, dst_len, got[0], want[0], got[2:], want[2:])
+        # (with n - 1 the reference stops at END_DST where its fast loop
+        # runs out of dst before it sees the padding, else at the error)
+        assert want[0] == O.ERROR if dst_len >= n \
+            else want[0] in (O.END_DST, O.ERROR)
+        if want[0] == O.END_DST:
+            assert got[1] == O.huff_decode(h)[1][:got[2]] and got[2] > 0
+
+
+@pytest.mark.gpu
 def test_decode_end_dst_caller_loop(shim):
     """The reference decoder's own loop on END_DST (lsqpack.c:3713-3742:
     keep the state, continue from n_src with a grown dst, final while input

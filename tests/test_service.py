@@ -116,6 +116,28 @@ def test_svc_random_round_trip(svc, n, lo, hi):
         check_dec(svc, enc, eo)
 
 
+def test_svc_layout_limits(svc):
+    """the strings that fill the decode kernels' LDS slots (limits.py), one
+    request: 66-byte strings of 5-bit codes (the fixed arena's limit),
+    128 / 129 / 200 bytes (the cooperative threshold, a full slot), periodic
+    strings of 63 segments (60 rounds and more of the cooperative decode's
+    round loop) and their invalid twins"""
+    import limits as L
+    D = L.DECODE_BY_NAME
+    strs = []
+    for name in ("fix66", "coop129", "coop63_504_ssi_lane29",
+                 "coop63_3024_0_lane63", "coop63_3024_rand_lane0"):
+        f = D[name]
+        strs += [f.tile[i] for i in f.special]
+    twins = [L.invalid_twin(h) for h in strs[::4]]
+    strs += twins
+    assert len(strs) <= 64 and sum(map(len, strs)) <= MAX_B
+    for base in (0, 5):
+        data, off = pack(strs, base=base)
+        _, _, st = check_dec(svc, data, off)
+        assert int(st.sum()) == len(twins)
+
+
 def test_svc_rejects_and_garbage(svc):
     """random bytes as Huffman input: mostly rejects (status 1, no output),
     some accepted -- exactly as the oracle says"""

@@ -440,6 +440,61 @@ def test_shapes(codec):
     run_rounds(codec, none_final, null_flags_when_none_final=False)
 
 
+def stage_edge_tile(longest, content):
+    """64 second chunks that are one staged tile of exactly 3072 bytes, all
+    5-bit codes behind a state 4 bits into code('0') (first pieces as
+    worst_case_batch): each fills floor((8 * len - 1) / 5) + 1 bytes, the
+    most a chunk can.  longest 65: ten chunks at kStreamFixMaxLen, the
+    fixed arena's limit; 66: ten more a byte past it, and the 3 * lane
+    variable arena packed to 3072 bytes of input.  content "zeros": code('0')
+    throughout (not final: the bits rarely end on a symbol); "f5": random
+    5-bit symbols, so that a misplaced byte shows, final with ones for
+    padding on every other chunk.  -> (first, second, finals)"""
+    rng = random.Random(longest)
+    lens = ([66] * 10 + [65] * 10 + [40] * 42 + [41] * 2 if longest == 66
+            else [65] * 20 + [40] * 32 + [41] * 12)
+    assert sum(lens) == 3072 and max(lens) == longest and len(lens) == 64
+    rng.shuffle(lens)
+    f5 = [s for s in range(256) if O.code_of(s)[1] == 5]
+    assert bytes(f5) == b"012aceiost"
+    second, finals = [], []
+    for i, ln in enumerate(lens):
+        if content == "zeros":
+            second.append(b"\0" * ln)
+            finals.append(False)
+            continue
+        k = (8 * ln - 1) // 5
+        bits = rng.choice("01") + "".join(code_bits(rng.choice(f5))
+                                          for _ in range(k))
+        c = bits_to_bytes(bits)
+        assert len(c) == ln and 8 * ln - len(bits) < 5
+        second.append(c)
+        finals.append(i % 2 == 0)
+    return [b"\0\0\0"] * 64, second, finals
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("content", ["zeros", "f5"])
+@pytest.mark.parametrize("longest", [65, 66])
+def test_stage_edge_tile(codec, longest, content):
+    """a staged tile of exactly 3072 bytes whose every chunk decodes to the
+    bound, with chunks at (65) and past (66) the fixed arena's limit"""
+    first, second, finals = stage_edge_tile(longest, content)
+    total = 0
+    for a, b, f in zip(first, second, finals):
+        st = fresh()
+        assert oracle_chunk(st, a, False)[:2] == (qhuff.DEC_MORE, b"0000")
+        ws, wo, _ = oracle_chunk(st, b, f)
+        assert ws == (qhuff.DEC_OK if f else qhuff.DEC_MORE)
+        assert len(wo) == (8 * len(b) - 1) // 5 + 1
+        total += len(wo)
+    assert total > 8 * 3072 // 5                 # more than 8/5 of the stage
+    st = run_rounds(codec, [(first, [False] * 64), (second, finals)])
+    assert (st[0] == qhuff.DEC_MORE).all()
+    assert (st[1] == [qhuff.DEC_OK if f else qhuff.DEC_MORE
+                      for f in finals]).all()
+
+
 # ---- the buffer contract ---------------------------------------------------------
 
 def carve(specs):

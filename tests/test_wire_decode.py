@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import _paths  # noqa: F401
+import limits
 import oracle_lib as O
 import qhuff
 import qpack_frames as Q
@@ -56,10 +57,16 @@ def lit(pos, payload, huffman, kind=qhuff.LIT_VALUE):
 
 
 class Shape:
-    def __init__(self, buf, lits, staged=None, unstaged=None):
+    def __init__(self, buf, lits, staged=None, unstaged=None, residue=None):
         self.buf, self.lits = bytes(buf), list(lits)
         assert qhuff.literals_check(self.lits) == (qhuff.OK, None)
-        if self.lits:
+        if residue is not None:
+            # a tile on the stage's edge: staged at this residue of the
+            # buffer's address and at no other
+            assert len(self.lits) == TILE
+            assert [r for r in range(16) if tile_staged(self.lits, r)[0]] \
+                == [residue]
+        elif self.lits:
             s, u = paths(self.lits)
             assert staged is None or s == staged
             assert unstaged is None or u == unstaged
@@ -177,7 +184,35 @@ def long_one(huffman, alone):
     return Shape(buf, lits, staged=False, unstaged=True)
 
 
-SHAPES = {"n0": lambda: counts(0), "n1": lambda: counts(1),
+@functools.lru_cache(maxsize=None)
+def stage_edge(longest):
+    """64 adjacent literals (no byte between them) that span exactly 3072
+    bytes: staged when the buffer is 16-byte aligned, in units at any other
+    residue.  Three in four are Huffman strings of 5-bit codes (they decode
+    to 8/5 of their length and fill their arena slots), the rest raw.
+    longest 66: twenty 66-byte literals, the fixed-stride arena's limit;
+    67: one of them a byte longer, and the variable arena packed to 3072
+    bytes of input."""
+    rng = random.Random(longest)
+    lens = [66] * 20 + [40] * 36 + [39] * 8
+    if longest == 67:
+        lens[0], lens[20] = 67, 39
+    assert sum(lens) == STAGE and max(lens) == longest
+    rng.shuffle(lens)
+    buf, lits = b"", []
+    for i, n in enumerate(lens):
+        raw = i % 4 == 3 and n < 66
+        s = bytes(rng.randrange(256) for _ in range(n)) if raw \
+            else limits.maxexp(n, rng)
+        lits.append(lit(len(buf), s, not raw))
+        buf += s
+    assert len(buf) == STAGE
+    return Shape(buf, lits, residue=0)
+
+
+SHAPES = {"edge3072_fix66": lambda: stage_edge(66),
+          "edge3072_var67": lambda: stage_edge(67),
+          "n0": lambda: counts(0), "n1": lambda: counts(1),
           "n63": lambda: counts(63), "n64": lambda: counts(64),
           "n65": lambda: counts(65), "n129": lambda: counts(129),
           "all_raw": all_raw, "all_empty": all_empty, "far_apart": far_apart,
@@ -460,6 +495,26 @@ def test_past_the_stage(codec, name):
     else:
         i = 0 if len(s.lits) == 1 else 29
         assert status[i] == 0 and outs[i] == long_text()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["edge3072_fix66", "edge3072_var67"])
+def test_stage_edge(codec, name):
+    """a tile of exactly 3072 bytes of adjacent literals at residue 0, its
+    Huffman literals at the 8/5 expansion (66 bytes: the fixed arena's
+    limit; 67: the variable arena, full): every literal against the oracle"""
+    s = SHAPES[name]()
+    assert tile_staged(s.lits, 0) == [True] and tile_staged(s.lits, 1) == [False]
+    outs, status = check_both(codec, s)
+    assert not any(status)
+    for l, o in zip(s.lits, outs):
+        payload = s.buf[l.pos:l.pos + l.len]
+        if l.huffman:
+            assert (O.OK, o) == O.huff_decode(payload)
+            assert len(o) == 8 * l.len // 5
+        else:
+            assert o == payload
+    assert sum(len(o) for o in outs) + 64 > STAGE
 
 
 @pytest.mark.gpu
