@@ -591,6 +591,15 @@ int qhuff_timing_read(qhuff_ctx *ctx, uint32_t *kind, double *us, uint32_t max);
  * bytes are the same either way. */
 int qhuff_kernel_variant(qhuff_ctx *ctx, int kind);
 
+/* Diagnostic: the most waves one launch of `kind` (QHUFF_KIND_ENCODE /
+ * _DECODE / _HASH) puts on the device -- workgroups per launch x waves per
+ * workgroup, after QHUFF_GRID_WG_PER_CU / QHUFF_GRID_PCT.  QHUFF_EINVAL for
+ * a null context or another kind.  Host arithmetic only.
+ * QHUFF_FEATURE_GRID_WAVES and the symbol announce it (the ABI version is
+ * unchanged). */
+#define QHUFF_FEATURE_GRID_WAVES 1
+int qhuff_grid_waves(qhuff_ctx *ctx, int kind);
+
 /* (ABI 6) The variant of the next launch of `kind` from what the caller
  * knows of its batch: hint 1 = the batch has
  * a string longer than 128 bytes or a 64-string tile spanning more than the

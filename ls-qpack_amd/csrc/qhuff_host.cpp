@@ -340,6 +340,8 @@ qhuff_open(int device, qhuff_ctx **ctx_out)
                 c->enc_grid = k * c->n_cu;
             if (k >= 1 && k <= (uint32_t) occ_d)
                 c->dec_grid = k * c->n_cu;
+            if (k >= 1 && k <= (uint32_t) occ_h)
+                c->hash_grid = k * c->n_cu;
         }
         // experiment: a percentage of the resident grid (half the CUs' worth
         // of workgroups at 50: per-CU vs chip-wide limits)
@@ -351,6 +353,7 @@ qhuff_open(int device, qhuff_ctx **ctx_out)
             {
                 c->enc_grid = c->enc_grid * q / 100 ? c->enc_grid * q / 100 : 1;
                 c->dec_grid = c->dec_grid * q / 100 ? c->dec_grid * q / 100 : 1;
+                c->hash_grid = c->hash_grid * q / 100 ? c->hash_grid * q / 100 : 1;
             }
         }
     }
@@ -704,6 +707,24 @@ qhuff_kernel_variant(qhuff_ctx *c, int kind)
     if (!c || (kind != QHUFF_KIND_ENCODE && kind != QHUFF_KIND_DECODE))
         return QHUFF_EINVAL;
     return c->last_full[kind] ? 1 : 0;
+}
+
+extern "C" int
+qhuff_grid_waves(qhuff_ctx *c, int kind)
+{
+    if (!c)
+        return QHUFF_EINVAL;
+    switch (kind)
+    {
+    case QHUFF_KIND_ENCODE:
+        return (int) (c->enc_grid * (uint32_t) encode_waves_per_block());
+    case QHUFF_KIND_DECODE:
+        return (int) (c->dec_grid * (uint32_t) decode_waves_per_block());
+    case QHUFF_KIND_HASH:
+        return (int) (c->hash_grid * (uint32_t) hash_waves_per_block());
+    default:
+        return QHUFF_EINVAL;
+    }
 }
 
 extern "C" int

@@ -45,6 +45,7 @@ EXPORTS = (
     "qhuff_decode_stream_bound", "qhuff_decode_stream",
     "qhuff_decode_stream_host",
     "qhuff_literals_check", "qhuff_decode_wire", "qhuff_decode_wire_host",
+    "qhuff_grid_waves",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -215,6 +216,8 @@ def lib():
         L.qhuff_timing_enable.argtypes = [vp, C.c_int]
         L.qhuff_kernel_variant.restype = C.c_int
         L.qhuff_kernel_variant.argtypes = [vp, C.c_int]
+        L.qhuff_grid_waves.restype = C.c_int
+        L.qhuff_grid_waves.argtypes = [vp, C.c_int]
         L.qhuff_batch_hint.restype = C.c_int
         L.qhuff_batch_hint.argtypes = [vp, C.c_int, C.c_int]
         L.qhuff_batch_needs_full.restype = C.c_int
@@ -591,6 +594,14 @@ class Codec:
         r = lib().qhuff_kernel_variant(self._ctx, kind)
         if r < 0:
             self._check(r, "qhuff_kernel_variant")
+        return r
+
+    def grid_waves(self, kind):
+        """qhuff_grid_waves: the most waves one launch of kind (KIND_ENCODE /
+        KIND_DECODE / KIND_HASH) puts on the device."""
+        r = lib().qhuff_grid_waves(self._ctx, kind)
+        if r < 0:
+            self._check(r, "qhuff_grid_waves")
         return r
 
     def batch_hint(self, kind, hint):

@@ -11,7 +11,9 @@ headers written out as numbers; DECODE and ENCODE name one tile per edge
 and side.
 tests/test_limits.py checks the fixtures against the model (CPU) and the
 kernels against the oracle on them (GPU); the wire, stream, service and
-shim tests take the same strings through their entry points.
+shim tests take the same strings through their entry points.  The header-
+hash kernel has a stage of its own: classify_hash() and HASH, at the end,
+with tests/test_hash_limits.py.
 """
 import random
 
@@ -649,3 +651,335 @@ def combined(fixtures, raw=False, repeat=1):
     strs += around(rng)
     data, off = pack(strs)
     return data, off, where
+
+
+# ---- the header-hash kernel (qhuff_hash.hip) ---------------------------------------
+#
+# The hash kernel has a stage of its own (kHashCap) and one comparison: a
+# tile whose 16-byte-aligned span fits the stage is copied to LDS and hashed
+# there (HashLds: dword reads that depend on the address mod 4, the last
+# stripe and word of a full stage reaching into the slack words), any other
+# is hashed from global memory by byte loads (HashGlb).  A tile is 64 strings
+# (qhuff_xxh32_batch) or 64 headers, 128 strings (qhuff_xxh32_headers).
+
+HASH_STAGE = 6144             # kHashCap = 64 * kHashNch * 16 (qhuff_hash.hip)
+HASH_NCH = 6                  # kHashNch: 16-byte chunks per lane
+HASH_SLACK_WORDS = 8          # HashWave::s: words past the stage
+
+assert HASH_STAGE == TS * HASH_NCH * 16
+
+
+def classify_hash(off, base_residue, pairs):
+    """Per tile of a hash batch -- 64 headers (pairs: off has 2n + 1
+    entries) or 64 strings (n + 1) -- as the kernel gets them, base_residue
+    the data pointer mod 16: span (tile_span's 16-byte-aligned bytes), n16
+    (its 16-byte chunks), staged (span <= 6144) and cnt (headers or strings
+    in the tile)."""
+    off = [int(x) for x in off]
+    k = 2 if pairs else 1
+    assert (len(off) - 1) % k == 0
+    n = (len(off) - 1) // k
+    tiles = []
+    for t0 in range(0, n, TS):
+        cnt = min(TS, n - t0)
+        span = _span(base_residue, off[k * t0], off[k * (t0 + cnt)])
+        tiles.append({"span": span, "n16": span // 16,
+                      "staged": span <= HASH_STAGE, "cnt": cnt})
+    return tiles
+
+
+LAYOUTS = ("pairs", "single")
+# the last-string lengths of hash_stage6144: the stripe's s[q + 4] (16, 32:
+# the last stripe ends the stage), the word tail's s[q + 1] (20: stripe then
+# word; 35: two stripes, then a byte tail only), the byte tail at the
+# stage's end (17, 19, 31).  A string that ends on the stage's last byte
+# starts at -len mod 4, so these give start & 3 in {0, 3, 1}; 18 and 34 are
+# added for start & 3 == 2.
+STAGE_LAST_LENS = (16, 17, 18, 19, 20, 31, 32, 34, 35)
+LONG_LENS = (6145, 70001)
+FILLER = 6200                 # one string that alone passes the stage
+
+
+class HashFixture:
+    """A run of whole tiles for the hash kernel (most fixtures: one tile).
+    strings[variant] is the run's strings for a layout variant ("single":
+    64 per tile; "pairs", "pairs_name", "pairs_value": 128 per tile, name
+    and value alternating); residues the alignments of the run's first byte;
+    want[r] whether its tiles are staged at residue r (one bool for all of
+    them), spans[r] the exact span of its first tile where the fixture
+    names one; last: the run ends in a partial tile and must end the
+    batch."""
+
+    def __init__(self, name, strings, want, edge, spans=None, twin=None,
+                 last=False):
+        self.name, self.strings, self.want, self.edge = name, strings, want, edge
+        self.residues = tuple(want)
+        self.spans, self.twin, self.last = spans or {}, twin, last
+
+    def variants(self):
+        return tuple(self.strings)
+
+    def __repr__(self):
+        return self.name
+
+
+def is_pairs(variant):
+    return variant != "single"
+
+
+def _rb(rng, n):
+    return rng.randbytes(n)
+
+
+def _split(rng, total, k):
+    """k lengths >= 0 that sum to total (some of them 0)"""
+    cuts = sorted(rng.randint(0, total) for _ in range(k - 1))
+    return [b - a for a, b in zip([0] + cuts, cuts + [total])]
+
+
+def hash_ordinary(rng, pairs, tiles=2):
+    """ordinary tiles for the hash kernel: random bytes, 8..40 a string
+    (at most 128 * 40 = 5120 bytes a tile: staged at any residue)"""
+    return [_rb(rng, rng.randint(8, 40))
+            for _ in range(TS * tiles * (2 if pairs else 1))]
+
+
+def lengths_run(rng, pairs, filler):
+    """Strings of every length 0..96 starting on every residue 0..15 (of a
+    run whose first byte is on residue 0), one after the other with no gap:
+    where no missing (length, residue) starts at the current residue, a
+    string of the set is repeated.  pairs: every (length, residue) once as
+    a name and once as a value.  Without filler every tile stays below the
+    stage (a string that would take it past ~6000 bytes waits, an empty one
+    takes its place); with filler every tile holds one string of FILLER
+    bytes, on a lane that moves from tile to tile.  The last tile is filled
+    up with repeats."""
+    roles = 2 if pairs else 1
+    per = TS * roles
+    need = {(p, r): set(range(97)) for p in range(roles) for r in range(16)}
+    left = 97 * 16 * roles
+    out, pos, tile_bytes = [], 0, 0
+    while left or len(out) % per:
+        i = len(out) % per
+        if i == 0:
+            tile_bytes = 0
+        if filler and i == (7 * (len(out) // per) + 3) % per:
+            out.append(_rb(rng, FILLER))
+            pos += FILLER
+            continue
+        room = 96 if filler else min(96, 6000 - tile_bytes)
+        p, r = len(out) % roles, pos % 16
+        # the next string's role and residue after a string of length l
+        def after(l):
+            return len(need[((p + 1) % roles, (r + l) % 16)])
+        cand = [l for l in need[(p, r)] if l <= room]
+        if cand:
+            best = max(after(l) for l in cand)
+            l = rng.choice([l for l in cand if after(l) == best])
+            need[(p, r)].discard(l)
+            left -= 1
+        elif room >= 16:
+            best = max(after(l) for l in range(1, 17))
+            l = rng.choice([l for l in range(1, 17) if after(l) == best])
+        else:
+            l = 0
+        out.append(_rb(rng, l))
+        pos += l
+        tile_bytes += l
+    return out
+
+
+def _hash_fixtures():
+    rng = random.Random(20242)
+    fx = []
+
+    def add(*a, **k):
+        fx.append(HashFixture(*a, **k))
+
+    def both(make):
+        return {v: make(is_pairs(v)) for v in LAYOUTS}
+
+    def cnt_of(pairs):
+        return TS * (2 if pairs else 1)
+
+    # span <= kHashCap: exactly 6144 bytes, the last string ending the stage
+    for ll in STAGE_LAST_LENS:
+        s = both(lambda pairs: [_rb(rng, n) for n in
+                                _split(rng, HASH_STAGE - ll, cnt_of(pairs) - 1)]
+                 + [_rb(rng, ll)])
+        add("hash_stage6144_len%d" % ll, s, {0: True},
+            "span <= kHashCap, at it: 6144 bytes at residue 0, n16 = 384, "
+            "the last string (%d bytes, start & 3 = %d) ends on the stage's "
+            "last byte" % (ll, -ll & 3), spans={0: HASH_STAGE},
+            twin="hash_stage6160_len%d" % ll)
+        add("hash_stage6160_len%d" % ll, s, {5: False},
+            "span <= kHashCap, past it: the same tile at residue 5, span "
+            "6160, hashed from global memory", spans={5: HASH_STAGE + 16},
+            twin="hash_stage6144_len%d" % ll)
+    # the largest skew on both sides of the edge
+    s = both(lambda pairs: [_rb(rng, n) for n in
+                            _split(rng, HASH_STAGE - 15 - 21,
+                                   cnt_of(pairs) - 1)] + [_rb(rng, 21)])
+    add("hash_stage_res15", s, {15: True}, "first byte at residue 15, last "
+        "byte the stage's last: skew 15, span 6144", spans={15: HASH_STAGE},
+        twin="hash_stage_res15_over")
+    s1 = {v: x[:-1] + [x[-1] + _rb(rng, 1)] for v, x in s.items()}
+    add("hash_stage_res15_over", s1, {15: False}, "the same one byte longer: "
+        "span 6160", spans={15: HASH_STAGE + 16}, twin="hash_stage_res15")
+    # one string that passes the stage alone, in the first or the last lane
+    for nm, lane in (("first", 0), ("last", 63)):
+        for ln in LONG_LENS:
+            def short(k):
+                return [_rb(rng, rng.choice([0, 0, 1, 3, 7, 12, 20, 33]))
+                        for _ in range(k)]
+            st = {"single": short(lane) + [_rb(rng, ln)] + short(63 - lane)}
+            for role in (0, 1):
+                x = short(128)
+                x[2 * lane + role] = _rb(rng, ln)
+                st["pairs_" + ("name", "value")[role]] = x
+            add("hash_%s_lane_long_%d" % (nm, ln), st, {0: False, 5: False},
+                "a string of %d bytes in lane %d (pairs: as a name, as a "
+                "value), short and empty ones beside it" % (ln, lane))
+    # partial last tiles: HashOffs::load's clamped lanes, last()
+    for cnt in (1, 2, 63):
+        for staged in (True, False):
+            def mk(pairs):
+                x = [_rb(rng, rng.choice([0, 2, 9, 17, 30, 41]))
+                     for _ in range(cnt * (2 if pairs else 1))]
+                if not staged:
+                    x[rng.randrange(len(x))] = _rb(rng, FILLER)
+                return x
+            add("hash_partial_%d_%s" % (cnt, "staged" if staged else "glb"),
+                both(mk), {0: staged, 5: staged}, "a last tile of %d, %s"
+                % (cnt, "staged" if staged else "past the stage"), last=True)
+    # length x alignment, through LDS and through global memory
+    add("hash_lengths", both(lambda pairs: lengths_run(rng, pairs, False)),
+        {0: True}, "every length 0..96 at every start residue 0..15, staged "
+        "tiles (HashLds)")
+    add("hash_lengths_glb", both(lambda pairs: lengths_run(rng, pairs, True)),
+        {0: False}, "the same with one string of 6200 bytes in every tile: "
+        "unstaged tiles (HashGlb)")
+    return fx
+
+
+HASH = _hash_fixtures()
+HASH_BY_NAME = {f.name: f for f in HASH}
+
+
+def pack_around(pre, run, post, residue, pad_front=True):
+    """pre + run + post packed, the run's first byte on `residue`: by
+    pad_front bytes in front of the data (to_dev) or, pad_front False, by
+    that many more bytes on the last string of pre -> (data, off, pad,
+    first tile of the run is at string index len(pre))"""
+    p = (residue - sum(len(s) for s in pre)) % 16
+    if not pad_front:
+        pre = pre[:-1] + [pre[-1] + bytes(range(100, 100 + p))]
+        p = 0
+    data, off = pack(pre + list(run) + post)
+    return data, off, p
+
+
+def hash_batch_of(f, variant, residue, pad_front=True):
+    """(data, off, pad_front, first tile, tiles) of fixture f's run in
+    layout `variant` between two ordinary tiles on either side (none after
+    a run that ends in a partial tile); off has n + 1 entries (single) or
+    2n + 1 (pairs)"""
+    pairs = is_pairs(variant)
+    rng = random.Random(len(f.name) * 139 + residue + 7 * len(variant))
+    pre = hash_ordinary(rng, pairs)
+    post = [] if f.last else hash_ordinary(rng, pairs)
+    run = f.strings[variant]
+    per = TS * (2 if pairs else 1)
+    assert f.last or len(run) % per == 0
+    data, off, pad = pack_around(pre, run, post, residue, pad_front)
+    ti = len(pre) // per
+    assert (int(off[len(pre)]) + pad) % 16 == residue
+    return data, off, pad, ti, -(-len(run) // per)
+
+
+def hash_oracle(data, off, pairs, seed):
+    """the oracle's hashes: (name_hash, nameval_hash) or (hash,)"""
+    if pairs:
+        return O.xxh32_headers(data, off, seed)
+    raw = data.tobytes()
+    return (np.array([O.xxh32(raw[int(off[i]):int(off[i + 1])], seed)
+                      for i in range(len(off) - 1)], dtype=np.uint32),)
+
+
+CHAIN_TILES = 640             # full tiles of the chain batch
+CHAIN_LAST = 37               # headers (strings) in its partial last tile
+
+
+def hash_chain(pairs):
+    """The multi-round batch: CHAIN_TILES full tiles and a last one of
+    CHAIN_LAST.  Every HASH fixture that is made of whole tiles is spliced
+    in once, at each of its residues (a few bytes more on the string in
+    front put it there); every other tile is staged (token-sized strings)
+    or not by a fixed-seed coin, the unstaged ones alternately one string of
+    6200 bytes among short ones and equal strings of about 50 (pairs) or
+    100 (single) bytes.  -> (data, off, [(fixture, residue, first tile)],
+    plan): plan[t] is what tile t was built to be (True staged, False not;
+    a fixture's tiles: its want); 16-byte-aligned buffer, off[0] = 0."""
+    rng = random.Random(4099 + pairs)
+    per = TS * (2 if pairs else 1)
+    runs = []
+    for f in HASH:
+        if f.last:
+            continue
+        for v in f.variants():
+            if is_pairs(v) == pairs:
+                for r in f.residues:
+                    runs.append((f, r, f.strings[v]))
+    n_fix = sum(len(s) // per for _, _, s in runs)
+    n_gen = CHAIN_TILES - n_fix
+    assert n_gen >= 2 * len(runs) + 300
+    # a run goes in after every `gap` generic tiles (never first)
+    gap = n_gen // (len(runs) + 1)
+    strs, where, plan, pos, alt, g = [], [], [], 0, 0, 0
+
+    def generic():
+        nonlocal alt
+        if rng.random() < 0.5:
+            plan.append(True)
+            return [_rb(rng, rng.randint(8, 40)) for _ in range(per)]
+        plan.append(False)
+        alt ^= 1
+        if alt:
+            x = [_rb(rng, rng.choice([0, 3, 8, 15, 22])) for _ in range(per)]
+            x[rng.randrange(TS) * (per // TS) + (per // TS - 1)] = \
+                _rb(rng, FILLER)
+            return x
+        return [_rb(rng, rng.randint(48, 53) * (2 if not pairs else 1))
+                for _ in range(per)]
+
+    for f, r, run in runs:
+        for _ in range(gap):
+            t = generic()
+            strs += t
+            pos += sum(len(s) for s in t)
+            g += 1
+        p = (r - pos) % 16
+        strs[-1] = strs[-1] + _rb(rng, p)
+        pos += p
+        assert pos % 16 == r and len(strs) % per == 0
+        where.append((f, r, len(strs) // per))
+        strs += run
+        plan += [f.want[r]] * (len(run) // per)
+        pos += sum(len(s) for s in run)
+    while g < n_gen:
+        strs += generic()
+        g += 1
+    assert len(strs) == CHAIN_TILES * per
+    strs += [_rb(rng, rng.randint(8, 40))
+             for _ in range(CHAIN_LAST * (per // TS))]
+    plan.append(True)
+    data, off = pack(strs)
+    return data, off, where, plan
+
+
+def transitions(staged, w):
+    """how often each (staged[t], staged[t + w]) occurs"""
+    c = {(a, b): 0 for a in (True, False) for b in (True, False)}
+    for a, b in zip(staged, staged[w:]):
+        c[(a, b)] += 1
+    return c

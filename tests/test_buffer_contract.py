@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 import _paths  # noqa: F401
+import limits
 import oracle_lib as O
 import qhuff
 import qpack_frames as Q
@@ -544,7 +545,11 @@ def hash_shape(kind):
         lens = [rng.choice([0, 1, 3, 4, 15, 16, 17, 31, 32, 33, 200])
                 for _ in range(2 * 1000)]
     elif kind == "long":                        # tiles larger than the stage
-        lens = [rng.randrange(0, 700) for _ in range(2 * 700)]
+        # (64 strings of 0..699 bytes never fit the hash kernel's 6144-byte
+        # stage: 128 headers of short ones follow, so that tiles on either
+        # side of it, and one that holds both kinds, are in the batch)
+        lens = [rng.randrange(0, 700) for _ in range(2 * 700)] \
+            + [rng.randrange(0, 40) for _ in range(2 * 128)]
     else:
         lens = [0] * (2 * 130)
     blob = bytes(rng.randrange(256) for _ in range(sum(lens)))
@@ -553,7 +558,21 @@ def hash_shape(kind):
     data = np.frombuffer(blob, dtype=np.uint8).copy()
     if kind == "long":
         assert (tile_stats(off[::2])[0] > workload.STAGE).any()
+        # the hash kernel's own stage, in both calls' layouts and at the
+        # residues test_device_hash_contract puts the batch on
+        for pairs in (True, False):
+            for res in (0, 1, 8, 13):
+                span = np.array([t["span"] for t in
+                                 limits.classify_hash(off, res, pairs)])
+                assert (span > limits.HASH_STAGE).any()
+                assert (span <= limits.HASH_STAGE).any()
     return data, off
+
+
+def test_hash_long_shape_reaches_both_sides():
+    """(CPU) hash_shape's own assertions"""
+    data, off = hash_shape("long")
+    assert len(off) % 2 == 1 and off[-1] == len(data)
 
 
 def hash_want(data, off, pairs):
@@ -700,13 +719,54 @@ def _top_bit_batch():
     return b
 
 
+TOP_R = (0, 1, 5, 12)       # the last string ends at 2^32 - 1 - r
+
+
+@functools.lru_cache(maxsize=None)
+def _top_bit_hash_batch(tail):
+    """~20 KB for the hash calls alone: token tiles, then 128 strings of
+    100 bytes or more, so that the last tile passes the hash kernel's stage
+    as 64 strings and as 64 headers and the batch ends in the reader of
+    global memory; the last string of 20 + tail bytes (tail 1..3: a stripe,
+    a word, then tail bytes whose p + 4 wraps where the string ends within
+    4 bytes of 2^32) -> (data, off, {pairs: hashes})"""
+    rng = random.Random(2 ** 32 + tail)
+    strs = rand_strings(rng, 128 * 2, ALPHAS["token"], 8, 40) \
+        + rand_strings(rng, 127, ALPHAS["all"], 100, 120) \
+        + rand_strings(rng, 1, ALPHAS["all"], 20 + tail, 20 + tail)
+    data, off = pack(strs)
+    assert len(off) - 1 == 3 * 128 and 1 <= tail <= 3
+    assert int(off[-1] - off[-2]) % 4 == tail and off[-1] - off[-2] >= 20
+    return data, off, {p: hash_want(data, off, p) for p in (True, False)}
+
+
+def test_top_bit_hash_batch_ends_unstaged():
+    """(CPU) at every place test_input_offsets_with_top_bit_set puts it,
+    the hash-only batch's last tile is past the hash kernel's stage in both
+    layouts (limits.classify_hash on the offsets the kernel gets: the
+    buffer is 16-byte aligned) and the tiles before it are staged"""
+    for tail in (1, 2, 3):
+        data, off, _ = _top_bit_hash_batch(tail)
+        for at in [(1 << 32) - 1 - r - len(data) for r in TOP_R] \
+                + [(1 << 31) - 5000]:
+            goff = off.astype(np.int64) + at
+            assert goff[-1] <= (1 << 32) - 1
+            for pairs in (True, False):
+                info = limits.classify_hash(goff, 0, pairs)
+                assert not info[-1]["staged"] and info[-1]["cnt"] == 64
+                assert info[0]["staged"] and info[1]["staged"]
+
+
 @pytest.mark.gpu
 def test_input_offsets_with_top_bit_set(codec):
     """in_off up to 2^32 - 1 and straddling 2^31 (uint32 offsets carried in
     int32 tensors): encode (modes 0, 7), decode and both hash calls,
     bit-exact with the oracle run on the same strings at offset 0.  The
     buffer is 2^32 bytes plus one page that no offset reaches, so the whole
-    16-byte block around the last string lies inside the allocation."""
+    16-byte block around the last string lies inside the allocation.  The
+    hash calls also run a batch of their own (_top_bit_hash_batch) whose
+    last tile is read from global memory and whose last string leaves 1, 2
+    and 3 tail bytes at 2^32 - 1 - r."""
     import torch
     b = _top_bit_batch()
     size = 1 << 32
@@ -714,7 +774,7 @@ def test_input_offsets_with_top_bit_set(codec):
     try:
         assert buf.data_ptr() % 16 == 0
         starts = {op: [size - 1 - r - int(b.inputs(op)[1][-1])
-                       for r in (0, 1, 5, 12)] + [(1 << 31) - 5000]
+                       for r in TOP_R] + [(1 << 31) - 5000]
                   for op in (0, "dec")}
         k = 0
         for i in range(5):
@@ -771,6 +831,40 @@ def test_input_offsets_with_top_bit_set(codec):
                 assert torch.equal(buf[at:end], dd)
                 assert np.array_equal(off_t.cpu().numpy().view(np.uint32), goff)
                 k += 1
+                if op not in ("hash", "headers"):
+                    continue
+                # the hash-only batch in the same buffer
+                for tail in (1, 2, 3):
+                    hd, hoff, hwant = _top_bit_hash_batch(tail)
+                    at = (size - 1 - TOP_R[i] - len(hd) if i < 4
+                          else (1 << 31) - 5000)
+                    end = at + len(hd)
+                    assert end <= size - 1 and end > 1 << 31
+                    if i < 4:
+                        assert end == size - 1 - TOP_R[i]
+                    dd = torch.from_numpy(hd).cuda()
+                    buf[at:end] = dd
+                    goff = (hoff.astype(np.uint64)
+                            + np.uint64(at)).astype(np.uint32)
+                    info = limits.classify_hash(goff, 0, pairs)
+                    assert not info[-1]["staged"]
+                    off_t = torch.from_numpy(goff.view(np.int32)).cuda()
+                    m = (len(hoff) - 1) // (2 if pairs else 1)
+                    ar = Arena([("h1", 4 * m, 4), ("h2", 4 * m if pairs else 0,
+                                                   12)], seed=4500 + k)
+                    ar.commit(True)
+                    device_hash_call(codec, pairs, m, buf.data_ptr(),
+                                     off_t.data_ptr(), ar.addr("h1"),
+                                     ar.addr("h2"))
+                    img = ar.after()
+                    want = hwant[pairs]
+                    assert np.array_equal(ar.get(img, "h1", np.uint32), want[0])
+                    if pairs:
+                        assert np.array_equal(ar.get(img, "h2", np.uint32),
+                                              want[1])
+                    ar.check(img, {"h1": 4 * m, "h2": 4 * m if pairs else 0})
+                    assert torch.equal(buf[at:end], dd)
+                    k += 1
     finally:
         del buf
         torch.cuda.empty_cache()
