@@ -496,6 +496,91 @@ int qhuff_decode_wire_host(qhuff_ctx *ctx, const uint8_t *buf,
                            uint32_t max_len, uint8_t *out, uint32_t *out_off,
                            uint8_t *status);
 
+/* ---- field lines and instructions encoded in one launch ------------------
+ * qhuff_encode_batch frames every literal of a launch with one prefix width
+ * and leaves the instruction bits and the prefixed integers between the
+ * literals -- static, dynamic and post-base indices, the field-section
+ * prefix -- to the host.  qhuff_encode_wire takes one descriptor per item and
+ * writes the wire bytes themselves: every instruction the reference's encoder
+ * writes (lsqpack_enc_encode, lsqpack.c:1963-2124) is an optional prefixed
+ * integer whose first byte carries the instruction bits, followed by an
+ * optional string literal, or a name literal whose first byte carries them,
+ * followed by a value literal; the field-section prefix (lsqpack.c:1277,
+ * 1296) is two integers.  qhuff_scan_field_section + qhuff_decode_wire read
+ * the output straight back.  QHUFF_FEATURE_ENCODE_WIRE and the symbols
+ * announce it (the ABI version is unchanged).
+ *
+ * Output of item i: out[out_off[i] .. out_off[i + 1]), two parts in this
+ * order --
+ *   1. int_bits != 0: ival as lsqpack_enc_int (lsqpack.c:787-814) writes it
+ *      with an int_bits-bit prefix into a first byte preset to int_first;
+ *   2. str_bits != 0: the bytes lsqpack_enc_enc_str(str_bits, ...) writes for
+ *      string i (in[in_off[i] .. in_off[i + 1])) with dst[0] = str_first
+ *      beforehand: the strict-< choice between Huffman and raw of
+ *      QHUFF_ENC_LITERAL3/5/7.
+ * With str_bits == 0 string i's bytes are ignored, whatever their length; an
+ * item with neither part emits nothing.  The outputs are concatenated in item
+ * order: a field section is a run of items, its length the difference of
+ * out_off at its ends.
+ *
+ * Item rule -- THE CALLER'S DUTY for qhuff_encode_wire, whose items are in
+ * device memory where the call cannot check them: int_bits <= 8 and
+ * int_first & ((1 << int_bits) - 1) == 0; str_bits one of 0, 3, 5, 7 and
+ * str_first & ((2 << str_bits) - 1) == 0; an unused part's *_first is 0.
+ * qhuff_items_check (host only) tests it: QHUFF_OK, or QHUFF_EINVAL with *bad
+ * (may be NULL) = the first offending index.  qhuff_encode_wire_host runs the
+ * check itself (QHUFF_EINVAL, nothing written).  The kernel masks what it
+ * reads: for items outside the rule their own bytes are unspecified, their
+ * size is at most 12 + the literal's payload, and all other items are
+ * unaffected -- the bound and the buffer contract hold for any descriptor
+ * bytes whatever.
+ *
+ * `out` must hold qhuff_encode_wire_bound(in_bytes, n) = ceil(30 * in_bytes /
+ * 8) + 13 * n + 16 bytes: per item 1 for byte rounding, 6 for the longest
+ * prefixed length and 6 for the longest 32-bit integer (a 1-bit prefix); the
+ * 16 are slack of the bound.
+ *
+ * The buffer contract above applies.  Writes: out[0 .. out_off[n]) and
+ * out_off[0 .. n], nothing else; for n = 0 only out_off[0].  Reads:
+ * items[0 .. n) (4-byte alignment is enough), in_off[0 .. n] and the
+ * 16-byte-aligned blocks that contain in[in_off[0] .. in_off[n]).  32-bit
+ * output offsets (the sticky QHUFF_DEVERR_RANGE) as qhuff_encode_batch;
+ * launches are timed as QHUFF_KIND_ENCODE.  The call does not consume
+ * qhuff_batch_hint and does not change what qhuff_kernel_variant reports.
+ * qhuff_encode_wire: device pointers (in, in_off, items, out, out_off),
+ * asynchronous on `stream`.  qhuff_encode_wire_host: host pointers,
+ * synchronous -- one upload, one launch, then the offsets and exactly
+ * out_off[n] bytes come back, with no loop over the items on the host but
+ * the check; QHUFF_ERANGE when the bound passes 32 bits.  Every item is coded by one lane, and a 64-item tile
+ * whose input span passes 3 KB, whose output passes 3008 bytes or whose
+ * Huffman codes together pass 24,576 bits leaves the byte-parallel path (the
+ * first two for the lean kernels' out-of-line path); no speed is promised
+ * for those. */
+#define QHUFF_FEATURE_ENCODE_WIRE 1
+
+struct qhuff_item {          /* 8 bytes, 4-byte aligned */
+    uint32_t ival;           /* the integer's value (int_bits != 0)            */
+    uint8_t  int_bits;       /* 0: no integer; 1..8: its prefix width          */
+    uint8_t  int_first;      /* OR-ed into the integer's first byte            */
+    uint8_t  str_bits;       /* 0: no literal; 3, 5 or 7: its length prefix    */
+    uint8_t  str_first;      /* OR-ed into the literal's first byte            */
+};
+
+uint64_t qhuff_encode_wire_bound(uint64_t in_bytes, uint32_t n);
+
+int qhuff_items_check(const struct qhuff_item *items, uint32_t n,
+                      uint32_t *bad);
+
+int qhuff_encode_wire(qhuff_ctx *ctx, const uint8_t *in,
+                      const uint32_t *in_off, const struct qhuff_item *items,
+                      uint32_t n, uint8_t *out, uint32_t *out_off,
+                      void *stream);
+
+int qhuff_encode_wire_host(qhuff_ctx *ctx, const uint8_t *in,
+                           const uint32_t *in_off,
+                           const struct qhuff_item *items, uint32_t n,
+                           uint8_t *out, uint32_t *out_off);
+
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman
  * payload was precomputed by a QHUFF_ENC_PAYLOAD batch (huff, huff_len =

@@ -999,6 +999,77 @@ qhuff_decode_wire(qhuff_ctx *c, const uint8_t *buf,
     return finish_launch(c, st);
 }
 
+// ---- items encoded in one launch (qhuff_encwire.hip) -----------------------
+
+extern "C" uint64_t
+qhuff_encode_wire_bound(uint64_t in_bytes, uint32_t n)
+{
+    // per item: 1 byte of rounding, 6 of prefixed length, 6 of integer
+    return (in_bytes * 30 + 7) / 8 + 13ull * n + 16;
+}
+
+extern "C" int
+qhuff_items_check(const struct qhuff_item *items, uint32_t n, uint32_t *bad)
+{
+    if (n && !items)
+        return QHUFF_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const struct qhuff_item &t = items[i];
+        const unsigned ib = t.int_bits, sb = t.str_bits;
+        // (an unused part's *_first: every bit counts)
+        const bool ok = ib <= 8
+                     && !(t.int_first & (ib ? (1u << ib) - 1 : 0xffu))
+                     && (sb == 0 || sb == 3 || sb == 5 || sb == 7)
+                     && !(t.str_first & (sb ? (2u << sb) - 1 : 0xffu));
+        if (!ok)
+        {
+            if (bad)
+                *bad = i;
+            return QHUFF_EINVAL;
+        }
+    }
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_encode_wire(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
+                  const struct qhuff_item *items, uint32_t n, uint8_t *out,
+                  uint32_t *out_off, void *stream)
+{
+    if (!c || !out_off || (n && (!in || !in_off || !items || !out)))
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    const uint64_t tiles = (n + kWT - 1) / kWT;
+    int rc = prepare_launch(c, tiles, st);
+    if (rc)
+        return rc;
+    EncArgs a;
+    a.in = in;
+    a.in_off = in_off;
+    a.out = out;
+    a.out_off = out_off;
+    a.enc = c->tab->enc;
+    a.n = n;
+    a.mode = 0;
+    a.c = coord(c, tiles);
+    // (the encode kernels' resident grid; the lean structure: no slots, no
+    // hint consumed, the batch kernel's last variant left as it is)
+    const uint64_t wpb = (uint64_t) encwire_waves_per_block();
+    const uint32_t grid = grid_for(c, tiles, wpb, c->enc_grid, &a.c.spread);
+    hipEvent_t e0, e1;
+    const uint32_t slot = timing_slot(c, QHUFF_KIND_ENCODE, &e0, &e1);
+    HIPCHK(c, launch_encwire(a, items, grid, st, e0, e1));
+    timing_commit(c, slot, QHUFF_KIND_ENCODE);
+    return finish_launch(c, st);
+}
+
 // ---- host helpers --------------------------------------------------------------
 
 extern "C" uint64_t

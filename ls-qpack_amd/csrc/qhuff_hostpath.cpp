@@ -899,6 +899,69 @@ qhuff_decode_wire_host(qhuff_ctx *c, const uint8_t *buf,
     return QHUFF_OK;
 }
 
+// Items encoded in one launch (qhuff_encode_wire): the strings, their
+// offsets and the items go up in one copy; one launch; the offsets come
+// back, then exactly the out_off[n] bytes written.  Nothing is framed or
+// spliced on the host: its only loop over the items is the rule's check.
+// Stage layout: [strings | in_off | items | out_off | out]; the kernel reads
+// the caller's offsets unchanged: `in` is passed rebased by -in_off[0].
+extern "C" int
+qhuff_encode_wire_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
+                       const struct qhuff_item *items, uint32_t n,
+                       uint8_t *out, uint32_t *out_off)
+{
+    if (!c || !out_off || (n && (!in || !in_off || !items || !out)))
+        return QHUFF_EINVAL;
+    if (qhuff_items_check(items, n, nullptr))
+        return QHUFF_EINVAL;
+    if (n == 0)
+    {
+        out_off[0] = 0;
+        return QHUFF_OK;
+    }
+    if (in_off[n] < in_off[0])
+        return QHUFF_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t a0 = in_off[0], bytes = (uint64_t) in_off[n] - a0;
+    const uint64_t bound = qhuff_encode_wire_bound(bytes, n);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const size_t o_io = up16(bytes) + 16;
+    const size_t o_it = o_io + up16(4ull * (n + 1));
+    const size_t o_oo = o_it + up16(8ull * n);
+    const size_t o_out = o_oo + up16(4ull * (n + 1));
+    int rc = ensure_stage(c, o_out + up16(bound));
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t sk = c->own_stream;
+    memcpy(H, in + a0, bytes);
+    memcpy(H + o_io, in_off, 4ull * (n + 1));
+    memcpy(H + o_it, items, 8ull * n);
+    HIPCHK(c, hipMemcpyAsync(D, H, o_oo, hipMemcpyHostToDevice, sk));
+    rc = qhuff_encode_wire(c, D - a0, (const uint32_t *) (D + o_io),
+                           (const struct qhuff_item *) (D + o_it), n,
+                           D + o_out, (uint32_t *) (D + o_oo), sk);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(H + o_oo, D + o_oo, o_out - o_oo,
+                             hipMemcpyDeviceToHost, sk));
+    HIPCHK(c, hipStreamSynchronize(sk));
+    rc = mirror_error(c);
+    if (rc)
+        return rc;
+    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
+    if (total)
+    {
+        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
+                                 hipMemcpyDeviceToHost, sk));
+        HIPCHK(c, hipStreamSynchronize(sk));
+        memcpy(out, H + o_out, total);
+    }
+    memcpy(out_off, H + o_oo, 4ull * (n + 1));
+    return QHUFF_OK;
+}
+
 // ---- header hashing, host buffers ----------------------------------------------
 
 // Stage layout: [name/value bytes | offsets (2n + 1) | name_hash | nameval_hash].

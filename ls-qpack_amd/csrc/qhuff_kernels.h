@@ -185,6 +185,13 @@ hipError_t launch_wire(const WireArgs &a, uint32_t grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t wire_occupancy(int *blocks_per_cu);
 int wire_waves_per_block();
+// items encoded in one launch (qhuff_encwire.hip): the encode arguments
+// (mode unused: every item has its own framing) and the n items
+hipError_t launch_encwire(const EncArgs &a, const ::qhuff_item *items,
+                          uint32_t grid, hipStream_t st,
+                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t encwire_occupancy(int *blocks_per_cu);
+int encwire_waves_per_block();
 hipError_t launch_hash(const HashArgs &a, uint32_t max_grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t hash_occupancy(int *blocks_per_cu);

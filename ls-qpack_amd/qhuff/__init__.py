@@ -46,6 +46,8 @@ EXPORTS = (
     "qhuff_decode_stream_host",
     "qhuff_literals_check", "qhuff_decode_wire", "qhuff_decode_wire_host",
     "qhuff_grid_waves",
+    "qhuff_encode_wire_bound", "qhuff_items_check", "qhuff_encode_wire",
+    "qhuff_encode_wire_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -70,6 +72,14 @@ class Literal(C.Structure):
                 ("huffman", C.c_uint8), ("prefix_bits", C.c_uint8),
                 ("kind", C.c_uint8), ("hdr_len", C.c_uint8),
                 ("instr", C.c_uint32)]
+
+
+class Item(C.Structure):
+    """struct qhuff_item (include/qhuff.h): one item of encode_wire -- an
+    optional prefixed integer, then an optional literal of string i"""
+    _fields_ = [("ival", C.c_uint32), ("int_bits", C.c_uint8),
+                ("int_first", C.c_uint8), ("str_bits", C.c_uint8),
+                ("str_first", C.c_uint8)]
 
 
 class Shard(C.Structure):
@@ -267,6 +277,16 @@ def lib():
         L.qhuff_decode_wire_host.restype = C.c_int
         L.qhuff_decode_wire_host.argtypes = [vp, vp, vp, C.c_uint32,
                                              C.c_uint32, vp, u32p, vp]
+        L.qhuff_encode_wire_bound.restype = C.c_uint64
+        L.qhuff_encode_wire_bound.argtypes = [C.c_uint64, C.c_uint32]
+        L.qhuff_items_check.restype = C.c_int
+        L.qhuff_items_check.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.qhuff_encode_wire.restype = C.c_int
+        L.qhuff_encode_wire.argtypes = [vp, vp, u32p, vp, C.c_uint32, vp,
+                                        u32p, vp]
+        L.qhuff_encode_wire_host.restype = C.c_int
+        L.qhuff_encode_wire_host.argtypes = [vp, vp, u32p, vp, C.c_uint32, vp,
+                                             u32p]
         _lib = L
     return _lib
 
@@ -365,6 +385,32 @@ def literals_bound(lits):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     return int(lib().qhuff_literals_bound(_np_ptr(a) if len(a) else None,
                                           len(a) // 16))
+
+
+def encode_wire_bound(in_bytes, n):
+    return int(lib().qhuff_encode_wire_bound(in_bytes, n))
+
+
+def items_array(items):
+    """[Item] -> the items as qhuff_encode_wire reads them: a numpy uint8
+    array of 8 * n bytes (torch.from_numpy(...).cuda() for the device
+    call)."""
+    import numpy as np
+    n = len(items)
+    arr = (Item * max(n, 1))(*items)
+    return np.frombuffer(bytes(arr), dtype=np.uint8)[:8 * n].copy()
+
+
+def items_check(items):
+    """qhuff_items_check: the item rule of encode_wire over [Item] (or their
+    uint8 array) -> (rc, first offending index or None)."""
+    import numpy as np
+    a = items if isinstance(items, np.ndarray) else items_array(items)
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    bad = C.c_uint32(0xffffffff)
+    rc = lib().qhuff_items_check(_np_ptr(a) if len(a) else None,
+                                 len(a) // 8, C.byref(bad))
+    return rc, (bad.value if rc != OK else None)
 
 
 def dec_int(buf, prefix_bits):
@@ -876,6 +922,48 @@ class Codec:
         self._check(rc, "qhuff_decode_wire_host")
         return ([out[out_off[i]:out_off[i + 1]].tobytes() for i in range(n)],
                 status[:n])
+
+    # field lines and instructions encoded in one launch ---------------------
+    def encode_wire_into(self, data, in_off, items, n, out, out_off,
+                         stream=None):
+        """qhuff_encode_wire: data the strings, in_off their n + 1 offsets,
+        items the n items (8 bytes each), all device tensors; the items must
+        satisfy the item rule (items_check)."""
+        rc = lib().qhuff_encode_wire(
+            self._ctx, data.data_ptr(), in_off.data_ptr(), items.data_ptr(),
+            n, out.data_ptr(), out_off.data_ptr(), self._stream(stream))
+        self._check(rc, "qhuff_encode_wire")
+
+    def encode_wire(self, data, in_off, items, stream=None):
+        """data: uint8 cuda tensor; in_off: int32 cuda tensor [n+1]; items:
+        uint8 cuda tensor of 8 * n bytes (items_array of [Item]).  Returns
+        (out uint8 [bound], out_off int32 [n+1])."""
+        import torch
+        n = in_off.numel() - 1
+        out = torch.empty(encode_wire_bound(int(data.numel()), n),
+                          dtype=torch.uint8, device=data.device)
+        out_off = torch.empty(n + 1, dtype=torch.int32, device=data.device)
+        self.encode_wire_into(data, in_off, items, n, out, out_off, stream)
+        return out, out_off
+
+    def encode_wire_host(self, data, in_off, items):
+        """qhuff_encode_wire_host over host buffers and [Item] (or their
+        uint8 array) -> (out uint8 ndarray [out_off[n]], out_off uint32
+        [n+1])."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint32)
+        a = items if isinstance(items, np.ndarray) else items_array(items)
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        n = len(in_off) - 1
+        out = np.zeros(encode_wire_bound(int(in_off[-1] - in_off[0]), n),
+                       dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint32)
+        rc = lib().qhuff_encode_wire_host(
+            self._ctx, _np_ptr(data), _np_ptr(in_off),
+            _np_ptr(a) if len(a) else None, n, _np_ptr(out), _np_ptr(out_off))
+        self._check(rc, "qhuff_encode_wire_host")
+        return out[:out_off[-1]], out_off
 
     def service(self, slots=0, idle_us=0):
         """Attach the low-latency service (qhuff_svc_open) -> Service."""
