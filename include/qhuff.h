@@ -215,6 +215,22 @@ int qhuff_svc_decode(qhuff_svc *svc, const uint8_t *in, const uint32_t *in_off,
 int qhuff_svc_stats(qhuff_svc *svc, uint64_t *served, uint64_t *launches,
                     uint64_t *fallbacks);
 
+/* Diagnostic: the pieces a service call of these n strings (in_off: n + 1
+ * host offsets) is cut into, one request slot each: at most 64 strings and
+ * 3072 input bytes a piece, a longer string alone.  Piece p is the strings
+ * [cuts[p], cuts[p + 1]): cuts[0] = 0 ... cuts[*n_pieces] = n, in an array
+ * of max_pieces + 1 entries.  QHUFF_OK; QHUFF_EINVAL for a null pointer or
+ * decreasing offsets; QHUFF_ERANGE when the call needs more than max_pieces
+ * pieces (*n_pieces is then the count needed, cuts holds the first
+ * max_pieces).  A call that would run the context's host path (more than
+ * QHUFF_SVC_MAX_STRINGS strings or QHUFF_SVC_MAX_BYTES bytes) reports
+ * *n_pieces = 0 with QHUFF_OK.  Host arithmetic only: no context, no device
+ * call.  QHUFF_FEATURE_SVC_PIECES and the symbol announce it (the ABI
+ * version is unchanged). */
+#define QHUFF_FEATURE_SVC_PIECES 1
+int qhuff_svc_pieces(const uint32_t *in_off, uint32_t n, uint32_t *cuts,
+                     uint32_t max_pieces, uint32_t *n_pieces);
+
 /* ---- per-string mirrors of the reference entry points -----------------
  * Same argument meaning, return values and error behaviour as the reference
  * functions; each call runs a one-string batch on the context's GPU (no CPU

@@ -356,6 +356,43 @@ svc_collect(qhuff_svc *v, uint32_t k, bool enc, uint32_t n, uint32_t base,
 // kSvcTileBytes input bytes; a longer string alone), one slot per piece: the
 // service codes a one-tile piece straight from its slot, and the pieces of
 // a call run on as many waves at once as there are free slots.
+
+// the end of the piece that starts at string s0 (s0 < n)
+static uint32_t
+svc_piece_end(const uint32_t *in_off, uint32_t s0, uint32_t n)
+{
+    uint32_t s1 = s0 + 1;
+    while (s1 < n && s1 - s0 < (uint32_t) kWT
+           && in_off[s1 + 1] - in_off[s0] <= kSvcTileBytes)
+        ++s1;
+    return s1;
+}
+
+// (diagnostic, host arithmetic only) the cuts svc_call makes
+extern "C" int
+qhuff_svc_pieces(const uint32_t *in_off, uint32_t n, uint32_t *cuts,
+                 uint32_t max_pieces, uint32_t *n_pieces)
+{
+    if (!in_off || !cuts || !n_pieces)
+        return QHUFF_EINVAL;
+    for (uint32_t i = 0; i < n; ++i)
+        if (in_off[i + 1] < in_off[i])
+            return QHUFF_EINVAL;
+    *n_pieces = 0;
+    cuts[0] = 0;
+    if (!svc_fits(in_off, n))                    // the context's host path
+        return QHUFF_OK;
+    uint32_t np = 0;
+    for (uint32_t s0 = 0; s0 < n; ++np)
+    {
+        s0 = svc_piece_end(in_off, s0, n);
+        if (np < max_pieces)
+            cuts[np + 1] = s0;
+    }
+    *n_pieces = np;
+    return np > max_pieces ? QHUFF_ERANGE : QHUFF_OK;
+}
+
 int
 qhuff::svc_call(qhuff_svc *v, bool enc, const uint8_t *in, const uint32_t *in_off,
          uint32_t n, unsigned mode, uint8_t *out, uint32_t *out_off,
@@ -393,10 +430,7 @@ qhuff::svc_call(qhuff_svc *v, bool enc, const uint8_t *in, const uint32_t *in_of
         p0[0] = s0;
         while (s0 < n && np < kMaxRound)
         {
-            uint32_t s1 = s0 + 1;
-            while (s1 < n && s1 - s0 < (uint32_t) kWT
-                   && in_off[s1 + 1] - in_off[s0] <= kSvcTileBytes)
-                ++s1;
+            const uint32_t s1 = svc_piece_end(in_off, s0, n);
             const uint32_t k = svc_take(v, np > 0);
             if (k == v->n_slots)
             {

@@ -37,7 +37,7 @@ EXPORTS = (
     "qhuff_decode_literals_ex", "qhuff_batch_hint", "qhuff_batch_needs_full",
     "qhuff_frame_literal", "qhuff_xxh32_headers_host",
     "qhuff_svc_open", "qhuff_svc_close", "qhuff_svc_encode",
-    "qhuff_svc_decode", "qhuff_svc_stats",
+    "qhuff_svc_decode", "qhuff_svc_stats", "qhuff_svc_pieces",
     "qhuff_timing_enable", "qhuff_timing_read", "qhuff_kernel_variant",
     "qhuff_dec_int", "qhuff_encode_batch_host_multi",
     "qhuff_decode_batch_host_multi", "qhuff_encode_batch_multi",
@@ -222,6 +222,9 @@ def lib():
         L.qhuff_svc_stats.argtypes = [vp, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64)]
+        L.qhuff_svc_pieces.restype = C.c_int
+        L.qhuff_svc_pieces.argtypes = [u32p, C.c_uint32, u32p, C.c_uint32,
+                                       C.POINTER(C.c_uint32)]
         L.qhuff_timing_enable.restype = C.c_int
         L.qhuff_timing_enable.argtypes = [vp, C.c_int]
         L.qhuff_kernel_variant.restype = C.c_int
@@ -320,6 +323,24 @@ def shard_cuts(in_off, g):
     if rc:
         raise QhuffError("qhuff_shard_cuts: %d" % rc)
     return cuts
+
+
+def svc_pieces(in_off, max_pieces=None):
+    """qhuff_svc_pieces: the string indices at which a service call of these
+    offsets is cut into pieces, [0, ..., n] -- [0] for a call that would run
+    the context's host path (or has no strings)."""
+    import numpy as np
+    in_off = np.ascontiguousarray(in_off, dtype=np.uint32)
+    n = len(in_off) - 1
+    if max_pieces is None:
+        max_pieces = max(n, 1)
+    cuts = np.zeros(max_pieces + 1, dtype=np.uint32)
+    k = C.c_uint32()
+    rc = lib().qhuff_svc_pieces(_np_ptr(in_off), n, _np_ptr(cuts), max_pieces,
+                                C.byref(k))
+    if rc:
+        raise QhuffError("qhuff_svc_pieces: %d (%d pieces)" % (rc, k.value))
+    return [int(x) for x in cuts[:k.value + 1]]
 
 
 def batch_needs_full(in_off):

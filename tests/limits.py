@@ -10,10 +10,13 @@ say which side of every comparison a tile is on, from the constants of the
 headers written out as numbers; DECODE and ENCODE name one tile per edge
 and side.
 tests/test_limits.py checks the fixtures against the model (CPU) and the
-kernels against the oracle on them (GPU); the wire, stream, service and
-shim tests take the same strings through their entry points.  The header-
-hash kernel has a stage of its own: classify_hash() and HASH, at the end,
-with tests/test_hash_limits.py.
+kernels against the oracle on them (GPU); the wire, stream and shim tests
+take some of the same strings through their entry points.  The resident
+service has a cutter and a tile loop of its own: svc_pieces(),
+classify_svc() / classify_svc_enc(), SVC_DECODE and SVC_ENCODE, with
+tests/test_service_limits.py, which also sends every DECODE and ENCODE tile
+through the service.  The header-hash kernel has a stage of its own:
+classify_hash() and HASH, at the end, with tests/test_hash_limits.py.
 """
 import random
 
@@ -271,6 +274,27 @@ def classify(off, base_residue, oracle_sizes):
     return tiles
 
 
+def _enc_unit(raw, off, sizes, res, mode, lo, hi, t0):
+    """EncPolicyT::codec_range / emit over the lanes [lo, hi) of the tile at
+    string t0 of the buffer raw (at `res` mod 16): se, dense, the output and
+    the lanes whose payload the whole wave copies"""
+    a, b = off[t0 + lo], off[t0 + hi]
+    lead = (res + a) % 16
+    se = code_bits(raw[a - lead:b]) if a >= lead else None
+    bits = [code_bits(raw[off[t0 + i]:off[t0 + i + 1]])
+            for i in range(lo, hi)]
+    ln = [off[t0 + i + 1] - off[t0 + i] for i in range(lo, hi)]
+    huff = [mode == 0 or (x + 7) // 8 < l for x, l in zip(bits, ln)]
+    out = sum(sizes[t0 + lo:t0 + hi])
+    dense = se is not None and se <= DENSE_MAX
+    emitted = dense and out <= OUT_FAST
+    return {"lo": lo, "hi": hi, "lone": False, "se": se, "dense": dense,
+            "out": out,
+            "coop": [lo + i for i in range(hi - lo)
+                     if emitted and huff[i] and sizes[t0 + lo + i]
+                     and bits[i] > ENC_COOP_BITS]}
+
+
 def classify_enc(data, off, base_residue, mode, oracle_sizes):
     """The same for an encode batch (EncPolicyT::codec_range / emit,
     enc_big_sizes): data the whole input buffer, off the n + 1 offsets into
@@ -289,21 +313,7 @@ def classify_enc(data, off, base_residue, mode, oracle_sizes):
     tiles = []
 
     def unit(lo, hi, t0):
-        a, b = off[t0 + lo], off[t0 + hi]
-        lead = (res + a) % 16
-        se = code_bits(raw[a - lead:b]) if a >= lead else None
-        bits = [code_bits(raw[off[t0 + i]:off[t0 + i + 1]])
-                for i in range(lo, hi)]
-        ln = [off[t0 + i + 1] - off[t0 + i] for i in range(lo, hi)]
-        huff = [mode == 0 or (x + 7) // 8 < l for x, l in zip(bits, ln)]
-        out = sum(sizes[t0 + lo:t0 + hi])
-        dense = se is not None and se <= DENSE_MAX
-        emitted = dense and out <= OUT_FAST
-        return {"lo": lo, "hi": hi, "lone": False, "se": se, "dense": dense,
-                "out": out,
-                "coop": [lo + i for i in range(hi - lo)
-                         if emitted and huff[i] and sizes[t0 + lo + i]
-                         and bits[i] > ENC_COOP_BITS]}
+        return _enc_unit(raw, off, sizes, res, mode, lo, hi, t0)
 
     for t0 in range(0, n, TS):
         cnt = min(TS, n - t0)
@@ -651,6 +661,380 @@ def combined(fixtures, raw=False, repeat=1):
     strs += around(rng)
     data, off = pack(strs)
     return data, off, where
+
+
+# ---- the resident service (qhuff_service.hip, qhuff_svc_host.cpp) ------------------
+#
+# The service runs the same policies behind a host cutter (svc_call) and in a
+# tile loop of its own (serve_tiles): svc_pieces() is the cutter,
+# classify_svc() / classify_svc_enc() the path of every piece, SVC_DECODE and
+# SVC_ENCODE whole calls that sit on the cutter's, the kernel's and copy2's
+# comparisons (tests/test_service_limits.py).
+
+SVC_MAX_STRINGS = 1024        # QHUFF_SVC_MAX_STRINGS = kSvcMaxStrings
+SVC_MAX_BYTES = 65536         # QHUFF_SVC_MAX_BYTES = kSvcInCap
+SVC_SLOTS = 12                # slots of a default service: one workgroup's waves
+COPY_PASS = 512               # copy2: 64 lanes x 8 chunks of 16 bytes a pass
+assert STAGE == 3072          # kSvcTileBytes == kStageCap (static_assert)
+
+
+def svc_pieces(off):
+    """svc_call's cutter (qhuff_svc_host.cpp, svc_piece_end), transcribed:
+    the string indices [0, ..., n] at which a call of these n + 1 offsets is
+    cut -- a piece takes strings while it has fewer than 64 and the next one
+    keeps it within 3072 bytes, its first string whatever its length; None
+    for a call that takes the context's host path (svc_fits)."""
+    off = [int(x) for x in off]
+    n = len(off) - 1
+    if n > SVC_MAX_STRINGS or off[n] - off[0] > SVC_MAX_BYTES:
+        return None
+    cuts, s0 = [0], 0
+    while s0 < n:
+        s1 = s0 + 1
+        while s1 < n and s1 - s0 < TS and off[s1 + 1] - off[s0] <= STAGE:
+            s1 += 1
+        cuts.append(s1)
+        s0 = s1
+    return cuts
+
+
+def _svc_piece(n, nb, total):
+    """what the two models share: the route (the kernel's `one`) and, for a
+    scratch piece, copy2's chunks and passes"""
+    p = {"n": n, "bytes": nb, "total": total,
+         "route": "direct" if n <= TS and nb <= STAGE else "scratch"}
+    if p["route"] == "scratch":
+        assert n == 1                        # the cutter leaves it alone
+        p["staged"], p["path"] = False, "slow"
+        p["copy_in"] = (4 * (n + 1) + 15) // 16 + (nb + 15) // 16
+        p["copy_out"] = (total + 15) // 16
+        p["passes_in"] = -(-p["copy_in"] // COPY_PASS)
+        p["passes_out"] = -(-p["copy_out"] // COPY_PASS)
+    else:
+        p["staged"] = True
+        p["path"] = "fast" if total <= OUT_FAST else "slow"
+    return p
+
+
+def classify_svc(off, oracle_sizes):
+    """The path of every piece of a decode call through the service
+    (svc_call, qhuff_service_kernel, serve_tiles): one dict per piece, or
+    None for a call that takes the host path.  What differs from classify():
+
+      * the residue is always 0: a piece's offsets are rebased to 0 and the
+        slot's regions are 256-aligned, so the span is the piece's bytes;
+      * a piece of at most 64 strings and 3072 bytes ("route": "direct") is
+        one tile coded straight from its slot, and always staged;
+      * there is no big slot, and the cooperative phase runs in the tile
+        loop itself: "path" is "fast" iff total <= 3008, cooperative
+        strings or not (DecPolicyT::emit copies them out of the arena with
+        the whole wave), else "slow": dec_slow_tile from the staged arena
+        into the slot;
+      * any other piece ("scratch") is one string of more than 3072 bytes,
+        copied to device scratch, sized and decoded there by its lane from
+        global memory, and copied back: copy2 moves 1 + ceil(bytes / 16)
+        chunks in (copy_in) and, after the chunk of offsets and the one of
+        the status, ceil(total / 16) chunks out (copy_out), 512 chunks a
+        pass (passes_in, passes_out).
+
+    Per piece: n, bytes, total, route, staged, path; a direct piece also has
+    _unit's arena, coop lanes, S, segs, slot_end and arena_cap."""
+    cuts = svc_pieces(off)
+    if cuts is None:
+        return None
+    sizes = [int(x) for x in oracle_sizes]
+    pieces = []
+    for s0, s1 in zip(cuts, cuts[1:]):
+        o = [int(off[i]) - int(off[s0]) for i in range(s0, s1 + 1)]
+        p = _svc_piece(s1 - s0, o[-1], sum(sizes[s0:s1]))
+        p.update(arena=None, coop=(), S=None, segs=())
+        if p["route"] == "direct":
+            u = _unit(o, sizes[s0:s1], 0, s1 - s0, 0)
+            p.update(arena=u["arena"], coop=tuple(u["coop"]), S=u.get("S"),
+                     segs=tuple(u.get("segs", ())), slot_end=u["slot_end"],
+                     arena_cap=u["arena_cap"])
+        pieces.append(p)
+    return pieces
+
+
+def classify_svc_enc(data, off, mode, oracle_sizes):
+    """The same for an encode call; what differs from classify_enc():
+
+      * residue 0, so se is the code bits of the piece's own bytes;
+      * a direct piece is always staged and dense-passed; "path" is "fast"
+        iff total <= 3008, else "slow": enc_slow_tile packs each lane's
+        string from the stage into the slot (no big slot);
+      * the wave copies a payload ("coop") only in a dense tile that is
+        emitted fast;
+      * a scratch piece is one string, sized and packed by its lane in
+        device memory (se None, not dense), with copy2's chunks as in
+        classify_svc.
+
+    Per piece: n, bytes, total, route, staged, path, se, dense, coop."""
+    cuts = svc_pieces(off)
+    if cuts is None:
+        return None
+    sizes = [int(x) for x in oracle_sizes]
+    raw = bytes(data)
+    pieces = []
+    for s0, s1 in zip(cuts, cuts[1:]):
+        a = int(off[s0])
+        o = [int(off[i]) - a for i in range(s0, s1 + 1)]
+        p = _svc_piece(s1 - s0, o[-1], sum(sizes[s0:s1]))
+        p.update(se=None, dense=False, coop=())
+        if p["route"] == "direct":
+            u = _enc_unit(raw[a:a + o[-1]], o, sizes[s0:s1], 0, mode, 0,
+                          s1 - s0, 0)
+            p.update(se=u["se"], dense=u["dense"], coop=tuple(u["coop"]))
+        pieces.append(p)
+    return pieces
+
+
+def token_huff(L, rng):
+    """the Huffman string, of exactly L bytes with 1..7 bits of padding, of
+    random token text (codes of 5..8 bits: a sum that grows by at most 8
+    cannot jump the 8 values that give L bytes)"""
+    s, bits = [], 0
+    while True:
+        while bits <= 8 * L - 8:
+            s.append(rng.choice(TOKEN))
+            bits += CODE_LEN[s[-1]]
+        if bits < 8 * L:
+            return _checked(bytes(s), L)
+        bits -= CODE_LEN[s.pop()]
+
+
+def padded5(L, rng, unit=None):
+    """L bytes of 5-bit codes with 1..5 bits of padding: maxexp(L) -- or
+    periodic(L, unit) -- with one symbol fewer where 8 L is a multiple of 5,
+    so that its invalid twin has L bytes too"""
+    n = (8 * L - 1) // 5
+    s = (unit * (n // len(unit) + 1))[:n] if unit else \
+        bytes(rng.choice(F5) for _ in range(n))
+    return _checked(s, L)
+
+
+def invalid_same_len(h):
+    """invalid_twin(h) for a string with padding, without that function's
+    bit-by-bit walk (strings of 64 KB): the last padding bit cleared, so
+    the string is rejected only at its very end"""
+    st, out = O.huff_decode(h)
+    assert st == O.OK and 1 <= 8 * len(h) - code_bits(out) < 8
+    t = h[:-1] + bytes([h[-1] & 0xfe])
+    assert O.huff_decode(t)[0] == O.ERROR and t[:-1] == h[:-1]
+    return t
+
+
+class SvcFixture:
+    """One service call: `strings` (Huffman strings for decode, raw ones for
+    encode in `mode`), `want` one dict per piece of the items its
+    classify_svc() / classify_svc_enc() entry must have, `bad` the strings
+    the oracle rejects, `edge` the comparison it sits on and `twin` the
+    fixture on the other side."""
+
+    def __init__(self, name, strings, want, edge, twin=None, mode=None,
+                 bad=0):
+        self.name, self.strings, self.want, self.edge = name, strings, want, edge
+        self.twin, self.mode, self.bad = twin, mode, bad
+        assert len(strings) <= SVC_MAX_STRINGS
+        assert sum(len(s) for s in strings) <= SVC_MAX_BYTES
+
+    def __repr__(self):
+        return self.name
+
+
+# input sizes of one string on the scratch route, in pairs across an edge:
+# the kernel's nb <= kStageCap (3072 | 3073), a whole last chunk or one byte
+# in the next (3088 | 3089), copy2's pass of 512 chunks counting the chunk of
+# offsets (511 chunks of input | 512, and 1023 | 1024), the slot's last byte
+SCRATCH_SIZES = (3073, 3088, 3089, 8176, 8177, 16368, 16369, 65535, 65536)
+SCRATCH_PASSES_IN = {3073: 1, 3088: 1, 3089: 1, 8176: 1, 8177: 2, 16368: 2,
+                     16369: 3, 65535: 9, 65536: 9}
+SCRATCH_TWIN = {3073: 3072, 3088: 3089, 3089: 3088, 8176: 8177, 8177: 8176,
+                16368: 16369, 16369: 16368, 65535: 65536, 65536: 65535}
+
+
+def _svc_name(size, tag):
+    return ("svc_one%d_%s" if size in (3072, 3073) else "svc_scr%d_%s") % (
+        size, tag)
+
+
+def _svc_decode_fixtures():
+    rng = random.Random(20243)
+    fx = []
+
+    def add(*a, **k):
+        fx.append(SvcFixture(*a, **k))
+
+    # total + 64 <= kOutCap with a cooperative string in the tile
+    ks = [45] * 28 + [44] * 35
+    rng.shuffle(ks)
+    t8 = [symbols(k, rng) for k in ks]
+    t8.insert(17, symbols(208, rng))
+    t9 = list(t8)
+    t9[40] = symbols(ks[39] + 1, rng)
+    assert len(t8[17]) == 130 and sum(len(s) for s in t9) < 2048
+    add("svc_coop_out3008", t8, [{"n": 64, "route": "direct", "path": "fast",
+                                  "total": 3008, "coop": (17,)}],
+        "total + 64 <= kOutCap in serve_tiles, at it, with a string of 130 "
+        "bytes: emitted fast, the cooperative string copied out of the "
+        "arena by DecPolicyT::emit", twin="svc_coop_out3009")
+    add("svc_coop_out3009", t9, [{"n": 64, "route": "direct", "path": "slow",
+                                  "total": 3009, "coop": (17,)}],
+        "the same, past it: 3009 bytes from the staged arena by "
+        "dec_slow_tile", twin="svc_coop_out3008")
+    # in_off[s1 + 1] - in_off[s0] <= kSvcTileBytes: strings of 64 bytes that
+    # decode to 60 (two 30-bit codes each), so the first piece is a fast one
+    s64 = [_checked(with_bits(60, 512, rng), 64) for _ in range(48)]
+    s65 = _checked(with_bits(61, 520, rng), 65)
+    tail = symbols(16, rng)
+    add("svc_cut3072", s64 + [tail],
+        [{"n": 48, "bytes": 3072, "route": "direct", "path": "fast"},
+         {"n": 1, "bytes": 10}],
+        "<= kSvcTileBytes, at it: 48 strings reach 3072 bytes, the next one "
+        "opens a piece", twin="svc_cut3073")
+    add("svc_cut3073", s64[:47] + [s65, tail],
+        [{"n": 47, "bytes": 3008}, {"n": 2, "bytes": 75}],
+        "<= kSvcTileBytes, past it: the 48th string would make 3073 bytes "
+        "and opens the second piece", twin="svc_cut3072")
+    # s1 - s0 < kWT
+    short = [symbols(rng.randint(8, 40), rng) for _ in range(65)]
+    add("svc_count65", short, [{"n": 64, "path": "fast"}, {"n": 1}],
+        "s1 - s0 < kWT: 65 short strings are cut (64, 1)")
+    add("svc_empty64_one", [b""] * 64 + [short[0]],
+        [{"n": 64, "bytes": 0, "total": 0, "path": "fast"}, {"n": 1}],
+        "s1 - s0 < kWT with no bytes at all: 64 empty strings are a piece "
+        "of zero bytes")
+    add("svc_3072_empties", [padded5(3072, rng)] + [b""] * 70,
+        [{"n": 64, "bytes": 3072, "route": "direct", "path": "slow",
+          "coop": (0,)}, {"n": 7, "bytes": 0, "total": 0}],
+        "both cuts: empty strings join a full 3072-byte piece until it has "
+        "64 strings, the other 7 are a piece of zero bytes")
+    add("svc_all_empty", [b""] * 70,
+        [{"n": 64, "bytes": 0}, {"n": 6, "bytes": 0}],
+        "a call of empty strings only: two pieces of zero bytes")
+    # nb <= kStageCap, and the scratch route's sizes
+    makers = (("maxexp", lambda L: padded5(L, rng)),
+              ("ssi", lambda L: padded5(L, rng, b"ssi")),
+              ("token", lambda L: token_huff(L, rng)))
+    for size in (3072,) + SCRATCH_SIZES:
+        for tag, mk in makers:
+            h = mk(size)
+            if size == 3072:
+                want = {"n": 1, "bytes": 3072, "route": "direct",
+                        "path": "slow", "coop": (0,)}
+                edge = "nb <= kStageCap, at it: one string of 3072 bytes, " \
+                       "staged and decoded by the whole wave"
+                twin = 3073
+            else:
+                want = {"n": 1, "bytes": size, "route": "scratch",
+                        "path": "slow", "copy_in": 1 + (size + 15) // 16,
+                        "passes_in": SCRATCH_PASSES_IN[size]}
+                edge = "one string of %d bytes through the scratch: %d " \
+                       "chunks in, %d pass(es) of copy2" % (
+                           size, want["copy_in"], want["passes_in"])
+                twin = SCRATCH_TWIN[size]
+            add(_svc_name(size, tag), [h], [want], edge,
+                twin=_svc_name(twin, tag))
+            # (3072: the whole wave finds the error, the lane decodes the
+            # string again and the tile, of no bytes, is emitted fast)
+            bad = dict(want, total=0)
+            if size == 3072:
+                bad.update(path="fast")
+            else:
+                bad.update(copy_out=0, passes_out=0)
+            add(_svc_name(size, tag) + "_invalid", [invalid_same_len(h)],
+                [bad], "the same string rejected at its very end: status 1, "
+                "no output" + ("" if size == 3072 else ", nothing copied "
+                               "back"), bad=1)
+    # copy2's pass on the way back
+    for k, twin in ((8192, 8193), (8193, 8192)):
+        add("svc_back%d" % k, [symbols(k, rng)],
+            [{"n": 1, "route": "scratch", "total": k,
+              "copy_out": (k + 15) // 16, "passes_out": 1 + (k > 8192)}],
+            "copy2's pass of 512 chunks on the way back: %d bytes out, "
+            "%d chunks" % (k, (k + 15) // 16), twin="svc_back%d" % twin)
+    return fx
+
+
+def _svc_encode_fixtures():
+    rng = random.Random(20244)
+    fx = []
+
+    def add(*a, **k):
+        k.setdefault("mode", 0)
+        fx.append(SvcFixture(*a, **k))
+
+    def tok(n):
+        return bytes(rng.choice(TOKEN) for _ in range(n))
+
+    s64 = [tok(64) for _ in range(48)]
+    add("svc_enc_cut3072", s64 + [tok(10)],
+        [{"n": 48, "bytes": 3072, "route": "direct", "path": "fast",
+          "dense": True}, {"n": 1, "bytes": 10}],
+        "<= kSvcTileBytes, at it: 48 strings reach 3072 bytes",
+        twin="svc_enc_cut3073")
+    add("svc_enc_cut3073", s64[:47] + [tok(65), tok(10)],
+        [{"n": 47, "bytes": 3008}, {"n": 2, "bytes": 75}],
+        "<= kSvcTileBytes, past it: the 48th string opens the second piece",
+        twin="svc_enc_cut3072")
+    short = [tok(rng.randint(8, 40)) for _ in range(65)]
+    add("svc_enc_count65", short, [{"n": 64, "path": "fast"}, {"n": 1}],
+        "s1 - s0 < kWT: 65 short strings are cut (64, 1)")
+    add("svc_enc_empty64_one", [b""] * 64 + [short[0]],
+        [{"n": 64, "bytes": 0, "se": 0, "path": "fast"}, {"n": 1}],
+        "64 empty strings are a piece of zero bytes")
+    add("svc_enc_3072_empties", [tok(3072)] + [b""] * 70,
+        [{"n": 64, "bytes": 3072, "route": "direct", "path": "fast",
+          "dense": True, "coop": (0,)}, {"n": 7, "bytes": 0}],
+        "both cuts: empty strings join a full piece until it has 64 strings, "
+        "the other 7 are a piece of zero bytes")
+    add("svc_enc_all_empty", [b""] * 70,
+        [{"n": 64, "bytes": 0}, {"n": 6, "bytes": 0}],
+        "a call of empty strings only")
+    makers = (("token", tok),
+              ("f5", lambda n: bytes(rng.choice(F5) for _ in range(n))),
+              ("b30", lambda n: bytes(rng.choice(B30) for _ in range(n))))
+    for size in (3072,) + SCRATCH_SIZES:
+        for tag, mk in makers:
+            if size == 3072:
+                # 3072 bytes of 30-bit codes are 92160 code bits: not dense,
+                # 11520 bytes packed by the lane from the stage
+                want = {"n": 1, "bytes": 3072, "route": "direct",
+                        "dense": tag != "b30",
+                        "path": "slow" if tag == "b30" else "fast",
+                        "coop": () if tag == "b30" else (0,)}
+                edge = "nb <= kStageCap, at it: one string of 3072 bytes, " \
+                       "staged"
+                twin = 3073
+            else:
+                want = {"n": 1, "bytes": size, "route": "scratch",
+                        "path": "slow", "dense": False,
+                        "copy_in": 1 + (size + 15) // 16,
+                        "passes_in": SCRATCH_PASSES_IN[size]}
+                edge = "one string of %d bytes through the scratch: %d " \
+                       "chunks in, %d pass(es) of copy2" % (
+                           size, want["copy_in"], want["passes_in"])
+                twin = SCRATCH_TWIN[size]
+            if tag == "b30":
+                want["total"] = (30 * size + 7) // 8
+            add(_svc_name(size, "enc_" + tag), [mk(size)], [want], edge,
+                twin=_svc_name(twin, "enc_" + tag))
+    for k, n, twin in ((8192, 13107, 8193), (8193, 13108, 8192)):
+        add("svc_enc_back%d" % k, [bytes(rng.choice(F5) for _ in range(n))],
+            [{"n": 1, "route": "scratch", "total": k,
+              "copy_out": (k + 15) // 16, "passes_out": 1 + (k > 8192)}],
+            "copy2's pass of 512 chunks on the way back: %d 5-bit codes, %d "
+            "bytes out" % (n, k), twin="svc_enc_back%d" % twin)
+    return fx
+
+
+SVC_DECODE = _svc_decode_fixtures()
+SVC_ENCODE = _svc_encode_fixtures()
+SVC_DECODE_BY_NAME = {f.name: f for f in SVC_DECODE}
+SVC_ENCODE_BY_NAME = {f.name: f for f in SVC_ENCODE}
+assert len(SVC_DECODE_BY_NAME) == len(SVC_DECODE)
+assert len(SVC_ENCODE_BY_NAME) == len(SVC_ENCODE)
 
 
 # ---- the header-hash kernel (qhuff_hash.hip) ---------------------------------------
