@@ -25,8 +25,6 @@
 // the look-back has resolved the tile's output base.
 #include "qhuff_decode_impl.h"
 
-#include <hip/hip_ext.h>
-
 // tickets claimed per wave in the prologue, at most (see qhuff_encode.hip)
 #ifndef QH_DEC_PER
 #define QH_DEC_PER 2
@@ -44,21 +42,9 @@ qhuff_decode_kernel(DecArgs a)
     QH_LDS DecSmem *sm = (QH_LDS DecSmem *) &smem;
     const int tid = threadIdx.x;
     prof_realtime(a.c, kProfIters - 1, 10);      // (profiling) wave entry
-    Tickets tk;
-    tk.init();
-    // The workgroup's ticket claims go out first, then every load of the
-    // tables; the claims are waited for (not the tables) and shared at the
-    // first barrier, each wave then issues its first offsets loads, and only
-    // then are the tables stored and the second barrier passed (in
-    // tile_pipeline's mid()): the offsets loads overlap the table loads.
-    const uint32_t cb = claim_block_issue(a.c, tk, QH_DEC_PER);
-    DecTableLoads tl;
-    tl.issue(a.win, a.sorted, a.long2, tid);
-    claim_block_store(a.c, cb, &sm->tk, QH_DEC_PER);
-    clear_next_launch(a.c);
-    // the tickets: LDS stores visible, no wait for the table loads (a
-    // __syncthreads() would drain them)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const auto p = dec_prologue<QH_DEC_PER>(a, sm, tid);
+    const Tickets &tk = p.tk;
+    const DecTableLoads tl = p.tl;
     prof_realtime(a.c, kProfIters - 1, 11);      // (profiling) after it
     DecPolicyT<DecSmem, Keep, Full> pol{a.in, sm,
                                   &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)], 0};
@@ -81,22 +67,13 @@ hipError_t
 launch_decode(const DecArgs &a, uint32_t grid, hipStream_t st, hipEvent_t ev0,
               hipEvent_t ev1, bool keep, bool full)
 {
+    // (the keep kernel is never timed)
     if (keep)
-        hipLaunchKernelGGL((qhuff_decode_kernel<true, false>), dim3(grid),
-                           dim3(64 * kWaves), 0, st, a);
-    else if (full && ev0)
-        hipExtLaunchKernelGGL((qhuff_decode_kernel<false, true>), dim3(grid),
-                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
-    else if (full)
-        hipLaunchKernelGGL((qhuff_decode_kernel<false, true>), dim3(grid),
-                           dim3(64 * kWaves), 0, st, a);
-    else if (ev0)
-        hipExtLaunchKernelGGL((qhuff_decode_kernel<false, false>), dim3(grid),
-                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
-    else
-        hipLaunchKernelGGL((qhuff_decode_kernel<false, false>), dim3(grid),
-                           dim3(64 * kWaves), 0, st, a);
-    return hipGetLastError();
+        return launch_kernel(qhuff_decode_kernel<true, false>, grid,
+                             64 * kWaves, st, nullptr, nullptr, a);
+    return launch_kernel(full ? qhuff_decode_kernel<false, true>
+                              : qhuff_decode_kernel<false, false>,
+                         grid, 64 * kWaves, st, ev0, ev1, a);
 }
 
 hipError_t

@@ -1456,4 +1456,45 @@ dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
     return fits;
 }
 
+// The prologue of the decode kernels (qhuff_decode.hip, qhuff_stream.hip,
+// qhuff_wire.hip).  The workgroup's ticket claims (Per a wave, at most) go
+// out first, then every load of the tables -- own(tid) starts a kernel's own
+// beside them (the stream kernel's nodes; NoTable: none); the claims are
+// waited for (not the tables) and shared at the first barrier.  Each wave
+// then issues its first offsets loads, and only then are the tables stored
+// and the second barrier passed (the kernel's tables() step, in
+// tile_pipeline's mid()): the offsets loads overlap the table loads.
+// (The state comes back by value, and no more than this is shared: with
+// wave_tickets in here, or the whole body in one function around a policy
+// maker, the kernels' registers and schedule change)
+struct NoTable
+{
+    __device__ __forceinline__ NoTable operator()(int) const { return {}; }
+};
+
+template <class X>
+struct DecPrologue
+{
+    Tickets tk;
+    DecTableLoads tl;
+    X own;
+};
+
+template <int Per, class SM, class Own = NoTable>
+__device__ __forceinline__ auto
+dec_prologue(const DecArgs &a, QH_LDS SM *sm, int tid, Own own = Own())
+{
+    DecPrologue<decltype(own(tid))> p;
+    p.tk.init();
+    const uint32_t cb = claim_block_issue(a.c, p.tk, Per);
+    p.tl.issue(a.win, a.sorted, a.long2, tid);
+    p.own = own(tid);
+    claim_block_store(a.c, cb, &sm->tk, Per);
+    clear_next_launch(a.c);
+    // the tickets: LDS stores visible, no wait for the table loads (a
+    // __syncthreads() would drain them)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    return p;
+}
+
 }  // namespace qhuff

@@ -31,8 +31,6 @@
 // (qhuff_pipeline.h).
 #include "qhuff_encode_impl.h"
 
-#include <hip/hip_ext.h>
-
 // tickets claimed per wave in the prologue, at most (tile_pipeline).  2: the
 // third and fourth tickets are claimed by each wave at its first top, after
 // every workgroup's first claims (tile_pipeline `late`).  3 (round 3,
@@ -52,15 +50,9 @@ qhuff_encode_kernel(EncArgs a)
     __shared__ EncSmem smem;
     QH_LDS EncSmem *sm = (QH_LDS EncSmem *) &smem;
     const int tid = threadIdx.x;
-    Tickets tk;
-    tk.init();
-    // the ticket atomics go out first (they queue behind every other
-    // workgroup's on the counters), then the table loads
-    const uint32_t cb = claim_block_issue(a.c, tk, QH_ENC_PER);
-    enc_tables_load(sm, a.enc, tid);
-    claim_block_store(a.c, cb, &sm->tk, QH_ENC_PER);
-    clear_next_launch(a.c);
-    __syncthreads();                 // the only workgroup barrier
+    const Tickets tk = enc_prologue<QH_ENC_PER>(a.c, &sm->tk, [sm, &a, tid] {
+        enc_tables_load(sm, a.enc, tid);
+    });
     EncPolicyT<EncSmem, Full> pol;
     pol.in = a.in;
     pol.mode = a.mode;
@@ -77,19 +69,9 @@ hipError_t
 launch_encode(const EncArgs &a, uint32_t grid, hipStream_t st, hipEvent_t ev0,
               hipEvent_t ev1, bool full)
 {
-    if (full && ev0)
-        hipExtLaunchKernelGGL(qhuff_encode_kernel<true>, dim3(grid),
-                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
-    else if (full)
-        hipLaunchKernelGGL(qhuff_encode_kernel<true>, dim3(grid),
-                           dim3(64 * kWaves), 0, st, a);
-    else if (ev0)
-        hipExtLaunchKernelGGL(qhuff_encode_kernel<false>, dim3(grid),
-                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
-    else
-        hipLaunchKernelGGL(qhuff_encode_kernel<false>, dim3(grid),
-                           dim3(64 * kWaves), 0, st, a);
-    return hipGetLastError();
+    return launch_kernel(full ? qhuff_encode_kernel<true>
+                              : qhuff_encode_kernel<false>,
+                         grid, 64 * kWaves, st, ev0, ev1, a);
 }
 
 hipError_t

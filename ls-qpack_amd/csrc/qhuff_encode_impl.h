@@ -1199,4 +1199,28 @@ enc_tables_load(QH_LDS SM *sm, const uint2 *enc_g, int tid)
     }
 }
 
+// The prologue of the encode kernels (qhuff_encode.hip, qhuff_encwire.hip):
+// the ticket atomics go out first (they queue behind every other
+// workgroup's on the counters), then the table loads (tables(): the
+// kernel's enc_tables_load); one workgroup barrier.  The tickets come back
+// by value (as dec_prologue's state, qhuff_decode_impl.h).  Two shapes keep
+// the kernels' code what it was: the table load is the kernel's own
+// callable (with the LDS pointer a parameter of this function its stores'
+// addresses are computed an instruction longer), and that callable captures
+// the thread id by value (by reference `tid >> 6` becomes an arithmetic
+// shift); DESIGN.md section 4.
+template <int Per, class Tables>
+__device__ __forceinline__ Tickets
+enc_prologue(const Coord &c, QH_LDS BlockTickets *bt, Tables tables)
+{
+    Tickets tk;
+    tk.init();
+    const uint32_t cb = claim_block_issue(c, tk, Per);
+    tables();
+    claim_block_store(c, cb, bt, Per);
+    clear_next_launch(c);
+    __syncthreads();                 // the only workgroup barrier
+    return tk;
+}
+
 }  // namespace qhuff

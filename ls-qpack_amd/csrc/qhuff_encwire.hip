@@ -24,8 +24,6 @@
 // No speed is promised for either.
 #include "qhuff_encwire_impl.h"
 
-#include <hip/hip_ext.h>
-
 #ifndef QH_ENC_PER
 #define QH_ENC_PER 2
 #endif
@@ -39,14 +37,9 @@ qhuff_encwire_kernel(EncWireArgs w)
     QH_LDS EncSmem *sm = (QH_LDS EncSmem *) &smem;
     const EncArgs &a = w.e;
     const int tid = threadIdx.x;
-    Tickets tk;
-    tk.init();
-    // the prologue of qhuff_encode_kernel
-    const uint32_t cb = claim_block_issue(a.c, tk, QH_ENC_PER);
-    enc_tables_load(sm, a.enc, tid);
-    claim_block_store(a.c, cb, &sm->tk, QH_ENC_PER);
-    clear_next_launch(a.c);
-    __syncthreads();                 // the only workgroup barrier
+    const Tickets tk = enc_prologue<QH_ENC_PER>(a.c, &sm->tk, [sm, &a, tid] {
+        enc_tables_load(sm, a.enc, tid);
+    });
     EncWirePolicyT<EncSmem> pol;
     pol.in = a.in;
     pol.sm = sm;
@@ -65,21 +58,8 @@ launch_encwire(const EncArgs &e, const ::qhuff_item *items, uint32_t grid,
     EncWireArgs a;
     a.items = items;
     a.e = e;
-    if (ev0)
-        hipExtLaunchKernelGGL(qhuff_encwire_kernel, dim3(grid),
-                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
-    else
-        hipLaunchKernelGGL(qhuff_encwire_kernel, dim3(grid),
-                           dim3(64 * kWaves), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t
-encwire_occupancy(int *blocks_per_cu)
-{
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        blocks_per_cu, reinterpret_cast<const void *>(qhuff_encwire_kernel),
-        64 * kWaves, 0);
+    return launch_kernel(qhuff_encwire_kernel, grid, 64 * kWaves, st, ev0,
+                         ev1, a);
 }
 
 int

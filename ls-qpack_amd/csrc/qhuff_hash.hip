@@ -22,8 +22,6 @@
 // costs its name + value bytes + 8 B of offsets + 8 B of hashes.
 #include "qhuff_kernels.h"
 
-#include <hip/hip_ext.h>
-
 namespace qhuff {
 
 constexpr int kHashWaves = 8;                      // waves per workgroup
@@ -263,13 +261,8 @@ launch_hash(const HashArgs &a, uint32_t max_grid, hipStream_t st,
     const uint64_t tiles = (a.n + kWT - 1) / kWT;
     const uint64_t need = (tiles + kHashWaves - 1) / kHashWaves;
     const uint32_t grid = (uint32_t) (need < max_grid ? need : max_grid);
-    if (ev0)
-        hipExtLaunchKernelGGL(qhuff_hash_kernel, dim3(grid),
-                              dim3(64 * kHashWaves), 0, st, ev0, ev1, 0, a);
-    else
-        hipLaunchKernelGGL(qhuff_hash_kernel, dim3(grid), dim3(64 * kHashWaves),
-                           0, st, a);
-    return hipGetLastError();
+    return launch_kernel(qhuff_hash_kernel, grid, 64 * kHashWaves, st, ev0,
+                         ev1, a);
 }
 
 // Shard stitching (qhuff_*_batch_multi): off[i] += add for i in [0, n],

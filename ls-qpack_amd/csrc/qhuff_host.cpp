@@ -520,16 +520,6 @@ prepare_launch(qhuff_ctx *c, uint64_t tiles, hipStream_t st)
     return QHUFF_OK;
 }
 
-// after a look-back launch on st (the ordering event is recorded only when
-// a later launch comes on another stream, see prepare_launch)
-static int
-finish_launch(qhuff_ctx *c, hipStream_t st)
-{
-    c->last_stream = st;
-    c->have_last = true;
-    return QHUFF_OK;
-}
-
 static Coord
 coord(qhuff_ctx *c, uint64_t tiles)
 {
@@ -587,6 +577,23 @@ timing_commit(qhuff_ctx *c, uint32_t k, uint32_t kind)
         return;
     c->t_kind[k] = (uint8_t) kind;
     ++c->t_next;
+}
+
+// One launch of `kind` inside its timing bracket: launch(e0, e1) sends it
+// with the slot's event pair (null: not timed) and returns the HIP error; the
+// slot is committed only once the launch has gone out.  `what` names the
+// launch in the context's error message.
+template <class F>
+static int
+timed(qhuff_ctx *c, uint32_t kind, const char *what, F launch)
+{
+    hipEvent_t e0, e1;
+    const uint32_t ts = timing_slot(c, kind, &e0, &e1);
+    const hipError_t e = launch(e0, e1);
+    if (e != hipSuccess)
+        return fail(c, e, what);
+    timing_commit(c, ts, kind);
+    return QHUFF_OK;
 }
 
 extern "C" int
@@ -657,10 +664,9 @@ qhuff_timing_read(qhuff_ctx *c, uint32_t *kind, double *us, uint32_t max)
 // add per workgroup on one counter, in order).  Larger batches: every wave,
 // ticket groups.
 static uint32_t
-grid_for(const qhuff_ctx *c, uint64_t tiles, uint64_t waves_per_block,
-         uint32_t cap, uint32_t *spread)
+grid_for(uint64_t tiles, uint64_t waves_per_block, uint32_t cap,
+         uint32_t *spread)
 {
-    (void) c;
     *spread = 0;
     if (tiles <= (uint64_t) cap * waves_per_block)
     {
@@ -737,26 +743,17 @@ qhuff_batch_hint(qhuff_ctx *c, int kind, int hint)
     return QHUFF_OK;
 }
 
-extern "C" int
-qhuff_encode_batch(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
-                   uint32_t n, unsigned mode, uint8_t *out, uint32_t *out_off,
-                   void *stream)
+// ---- the tile calls' launch frame ------------------------------------------
+//
+// qhuff_encode_batch, qhuff_decode_batch, qhuff_decode_stream,
+// qhuff_decode_wire and qhuff_encode_wire check their own arguments and then
+// go through tile_launch; what differs between them is the body.
+
+static EncArgs
+enc_args(const qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
+         uint8_t *out, uint32_t *out_off, uint32_t n, unsigned mode,
+         const Coord &k)
 {
-    if (!c || !in_off || !out_off || (n && (!in || !out)))
-        return QHUFF_EINVAL;
-    if (mode != 0 && mode != 3 && mode != 5 && mode != 7)
-        return QHUFF_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n == 0)
-    {
-        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
-        return QHUFF_OK;
-    }
-    uint64_t tiles = (n + kWT - 1) / kWT;
-    int rc = prepare_launch(c, tiles, st);
-    if (rc)
-        return rc;
     EncArgs a;
     a.in = in;
     a.in_off = in_off;
@@ -765,43 +762,15 @@ qhuff_encode_batch(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
     a.enc = c->tab->enc;
     a.n = n;
     a.mode = mode;
-    a.c = coord(c, tiles);
-    const uint64_t wpb = (uint64_t) encode_waves_per_block();
-    const uint32_t grid = grid_for(c, tiles, wpb, c->enc_grid, &a.c.spread);
-    bool full = pick_full(c, 0);
-    rc = with_slots(c, grid, wpb, &full, st, [&](uint8_t *slots) -> int {
-        a.c.big = slots;
-        hipEvent_t e0, e1;
-        const uint32_t ts = timing_slot(c, QHUFF_KIND_ENCODE, &e0, &e1);
-        HIPCHK(c, launch_encode(a, grid, st, e0, e1, full));
-        timing_commit(c, ts, QHUFF_KIND_ENCODE);
-        return QHUFF_OK;
-    });
-    if (rc)
-        return rc;
-    c->last_full[0] = full;
-    return finish_launch(c, st);
+    a.c = k;
+    return a;
 }
 
-extern "C" int
-qhuff_decode_batch(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
-                   uint32_t n, uint8_t *out, uint32_t *out_off,
-                   uint8_t *status, void *stream)
+static DecArgs
+dec_args(const qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
+         uint8_t *out, uint32_t *out_off, uint8_t *status, uint32_t n,
+         const Coord &k)
 {
-    if (!c || !in_off || !out_off || (n && (!in || !out || !status)))
-        return QHUFF_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n == 0)
-    {
-        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
-        return QHUFF_OK;
-    }
-    const uint64_t ts = decode_tile_strings();
-    uint64_t tiles = (n + ts - 1) / ts;
-    int rc = prepare_launch(c, tiles, st);
-    if (rc)
-        return rc;
     DecArgs a;
     a.in = in;
     a.in_off = in_off;
@@ -812,31 +781,111 @@ qhuff_decode_batch(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
     a.sorted = c->tab->sorted;
     a.long2 = c->tab->long2;
     a.n = n;
-    a.c = coord(c, tiles);
+    a.c = k;
     a.lp = c->lp;
-    const uint64_t wpb = (uint64_t) decode_waves_per_block();
-    const uint32_t grid = grid_for(c, tiles, wpb, c->dec_grid, &a.c.spread);
-    // (keep: the per-string replay -- the lean keep kernel, never timed, and
-    // outside the variant choice of the batch kernel: ADVICE r04)
-    bool full = false;
-    if (!c->keep_rejected)
-        full = pick_full(c, 1);
-    else
-        c->hint[1] = -1;                 // (consumed by this launch too)
-    rc = with_slots(c, grid, wpb, &full, st, [&](uint8_t *slots) -> int {
-        a.c.big = slots;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const uint32_t ts = c->keep_rejected
-            ? kNoTiming : timing_slot(c, QHUFF_KIND_DECODE, &e0, &e1);
-        HIPCHK(c, launch_decode(a, grid, st, e0, e1, c->keep_rejected, full));
-        timing_commit(c, ts, QHUFF_KIND_DECODE);
+    return a;
+}
+
+// One launch over n strings in tiles of `tile_strings`, by a kernel of `wpb`
+// waves a workgroup on at most `cap` workgroups (its family's resident grid:
+// the tiles are claimed from tickets, so any grid is correct).  n == 0
+// writes out_off[0] and launches nothing.  Otherwise the look-back workspace
+// is prepared, body(k, grid) fills its argument block around the launch's
+// Coord k (spread set, big null) and launches on st; the context remembers
+// the stream of a launch that went out (the ordering event is recorded only
+// when a later launch comes on another stream, see prepare_launch).
+template <class F>
+static int
+tile_launch(qhuff_ctx *c, uint32_t n, uint64_t tile_strings, uint64_t wpb,
+            uint32_t cap, uint32_t *out_off, hipStream_t st, F body)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
         return QHUFF_OK;
-    });
+    }
+    const uint64_t tiles = (n + tile_strings - 1) / tile_strings;
+    int rc = prepare_launch(c, tiles, st);
     if (rc)
         return rc;
-    if (!c->keep_rejected)
-        c->last_full[1] = full;
-    return finish_launch(c, st);
+    Coord k = coord(c, tiles);
+    const uint32_t grid = grid_for(tiles, wpb, cap, &k.spread);
+    rc = body(k, grid);
+    if (rc)
+        return rc;
+    c->last_stream = st;
+    c->have_last = true;
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_encode_batch(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
+                   uint32_t n, unsigned mode, uint8_t *out, uint32_t *out_off,
+                   void *stream)
+{
+    if (!c || !in_off || !out_off || (n && (!in || !out)))
+        return QHUFF_EINVAL;
+    if (mode != 0 && mode != 3 && mode != 5 && mode != 7)
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    const uint64_t wpb = (uint64_t) encode_waves_per_block();
+    return tile_launch(c, n, kWT, wpb, c->enc_grid, out_off, st,
+                       [&](const Coord &k, uint32_t grid) -> int {
+        EncArgs a = enc_args(c, in, in_off, out, out_off, n, mode, k);
+        bool full = pick_full(c, 0);
+        const int rc = with_slots(c, grid, wpb, &full, st,
+                                  [&](uint8_t *slots) -> int {
+            a.c.big = slots;
+            return timed(c, QHUFF_KIND_ENCODE, "launch_encode",
+                         [&](hipEvent_t e0, hipEvent_t e1) {
+                return launch_encode(a, grid, st, e0, e1, full);
+            });
+        });
+        if (rc == QHUFF_OK)
+            c->last_full[0] = full;
+        return rc;
+    });
+}
+
+extern "C" int
+qhuff_decode_batch(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
+                   uint32_t n, uint8_t *out, uint32_t *out_off,
+                   uint8_t *status, void *stream)
+{
+    if (!c || !in_off || !out_off || (n && (!in || !out || !status)))
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    const uint64_t wpb = (uint64_t) decode_waves_per_block();
+    return tile_launch(c, n, decode_tile_strings(), wpb, c->dec_grid, out_off,
+                       st, [&](const Coord &k, uint32_t grid) -> int {
+        DecArgs a = dec_args(c, in, in_off, out, out_off, status, n, k);
+        // (keep: the per-string replay -- the lean keep kernel, never timed,
+        // and outside the variant choice of the batch kernel: ADVICE r04)
+        const bool keep = c->keep_rejected;
+        bool full = false;
+        if (!keep)
+            full = pick_full(c, 1);
+        else
+            c->hint[1] = -1;             // (consumed by this launch too)
+        const int rc = with_slots(c, grid, wpb, &full, st,
+                                  [&](uint8_t *slots) -> int {
+            a.c.big = slots;
+            if (keep)
+            {
+                HIPCHK(c, launch_decode(a, grid, st, nullptr, nullptr, true,
+                                        full));
+                return QHUFF_OK;
+            }
+            return timed(c, QHUFF_KIND_DECODE, "launch_decode",
+                         [&](hipEvent_t e0, hipEvent_t e1) {
+                return launch_decode(a, grid, st, e0, e1, false, full);
+            });
+        });
+        if (rc == QHUFF_OK && !keep)
+            c->last_full[1] = full;
+        return rc;
+    });
 }
 
 // ---- header hashing ---------------------------------------------------------
@@ -860,11 +909,10 @@ hash_call(qhuff_ctx *c, const uint8_t *in, const uint32_t *off, uint32_t n,
     a.n = n;
     a.seed = seed;
     a.pairs = pairs ? 1u : 0u;
-    hipEvent_t e0, e1;
-    const uint32_t ts = timing_slot(c, QHUFF_KIND_HASH, &e0, &e1);
-    HIPCHK(c, launch_hash(a, c->hash_grid, (hipStream_t) stream, e0, e1));
-    timing_commit(c, ts, QHUFF_KIND_HASH);
-    return QHUFF_OK;
+    return timed(c, QHUFF_KIND_HASH, "launch_hash",
+                 [&](hipEvent_t e0, hipEvent_t e1) {
+        return launch_hash(a, c->hash_grid, (hipStream_t) stream, e0, e1);
+    });
 }
 
 extern "C" int
@@ -916,41 +964,21 @@ qhuff_decode_stream(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
     if (!c || !in_off || !out_off || (n && (!in || !out || !status || !state)))
         return QHUFF_EINVAL;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n == 0)
-    {
-        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
-        return QHUFF_OK;
-    }
-    const uint64_t ts = decode_tile_strings();
-    const uint64_t tiles = (n + ts - 1) / ts;
-    int rc = prepare_launch(c, tiles, st);
-    if (rc)
-        return rc;
-    StreamArgs a;
-    a.d.in = in;
-    a.d.in_off = in_off;
-    a.d.out = out;
-    a.d.out_off = out_off;
-    a.d.status = status;
-    a.d.win = c->tab->win;
-    a.d.sorted = c->tab->sorted;
-    a.d.long2 = c->tab->long2;
-    a.d.n = n;
-    a.d.c = coord(c, tiles);
-    a.d.lp = c->lp;
-    a.nodes = c->tab->nodes;
-    a.state = state;
-    a.flags = flags;
-    // (the decode kernels' resident grid: the tiles are claimed from
-    // tickets, so any grid is correct)
-    const uint64_t wpb = (uint64_t) stream_waves_per_block();
-    const uint32_t grid = grid_for(c, tiles, wpb, c->dec_grid, &a.d.c.spread);
-    hipEvent_t e0, e1;
-    const uint32_t slot = timing_slot(c, QHUFF_KIND_DECODE, &e0, &e1);
-    HIPCHK(c, launch_stream(a, grid, st, e0, e1));
-    timing_commit(c, slot, QHUFF_KIND_DECODE);
-    return finish_launch(c, st);
+    // (the lean structure, here and in the two calls below: no slots, no
+    // hint consumed, the batch kernel's last variant left as it is)
+    return tile_launch(c, n, decode_tile_strings(), stream_waves_per_block(),
+                       c->dec_grid, out_off, st,
+                       [&](const Coord &k, uint32_t grid) -> int {
+        StreamArgs a;
+        a.d = dec_args(c, in, in_off, out, out_off, status, n, k);
+        a.nodes = c->tab->nodes;
+        a.state = state;
+        a.flags = flags;
+        return timed(c, QHUFF_KIND_DECODE, "launch_stream",
+                     [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_stream(a, grid, st, e0, e1);
+        });
+    });
 }
 
 // ---- literals in place (qhuff_wire.hip) ------------------------------------
@@ -964,39 +992,19 @@ qhuff_decode_wire(qhuff_ctx *c, const uint8_t *buf,
     if (!c || !out_off || (n && (!buf || !lits || !out || !status)))
         return QHUFF_EINVAL;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n == 0)
-    {
-        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
-        return QHUFF_OK;
-    }
-    const uint64_t ts = decode_tile_strings();
-    const uint64_t tiles = (n + ts - 1) / ts;
-    int rc = prepare_launch(c, tiles, st);
-    if (rc)
-        return rc;
-    WireArgs a;
-    a.d.in = buf;
-    // (the tile pipeline's offsets pointer: the policy reads descriptors)
-    a.d.in_off = (const uint32_t *) lits;
-    a.d.out = out;
-    a.d.out_off = out_off;
-    a.d.status = status;
-    a.d.win = c->tab->win;
-    a.d.sorted = c->tab->sorted;
-    a.d.long2 = c->tab->long2;
-    a.d.n = n;
-    a.d.c = coord(c, tiles);
-    a.d.lp = c->lp;
-    a.max_len = max_len;
-    // (the decode kernels' resident grid, as qhuff_decode_stream)
-    const uint64_t wpb = (uint64_t) wire_waves_per_block();
-    const uint32_t grid = grid_for(c, tiles, wpb, c->dec_grid, &a.d.c.spread);
-    hipEvent_t e0, e1;
-    const uint32_t slot = timing_slot(c, QHUFF_KIND_DECODE, &e0, &e1);
-    HIPCHK(c, launch_wire(a, grid, st, e0, e1));
-    timing_commit(c, slot, QHUFF_KIND_DECODE);
-    return finish_launch(c, st);
+    return tile_launch(c, n, decode_tile_strings(), wire_waves_per_block(),
+                       c->dec_grid, out_off, st,
+                       [&](const Coord &k, uint32_t grid) -> int {
+        WireArgs a;
+        // (the tile pipeline's offsets pointer: the policy reads descriptors)
+        a.d = dec_args(c, buf, (const uint32_t *) lits, out, out_off, status,
+                       n, k);
+        a.max_len = max_len;
+        return timed(c, QHUFF_KIND_DECODE, "launch_wire",
+                     [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_wire(a, grid, st, e0, e1);
+        });
+    });
 }
 
 // ---- items encoded in one launch (qhuff_encwire.hip) -----------------------
@@ -1040,34 +1048,15 @@ qhuff_encode_wire(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
     if (!c || !out_off || (n && (!in || !in_off || !items || !out)))
         return QHUFF_EINVAL;
     hipStream_t st = (hipStream_t) stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (n == 0)
-    {
-        HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
-        return QHUFF_OK;
-    }
-    const uint64_t tiles = (n + kWT - 1) / kWT;
-    int rc = prepare_launch(c, tiles, st);
-    if (rc)
-        return rc;
-    EncArgs a;
-    a.in = in;
-    a.in_off = in_off;
-    a.out = out;
-    a.out_off = out_off;
-    a.enc = c->tab->enc;
-    a.n = n;
-    a.mode = 0;
-    a.c = coord(c, tiles);
-    // (the encode kernels' resident grid; the lean structure: no slots, no
-    // hint consumed, the batch kernel's last variant left as it is)
-    const uint64_t wpb = (uint64_t) encwire_waves_per_block();
-    const uint32_t grid = grid_for(c, tiles, wpb, c->enc_grid, &a.c.spread);
-    hipEvent_t e0, e1;
-    const uint32_t slot = timing_slot(c, QHUFF_KIND_ENCODE, &e0, &e1);
-    HIPCHK(c, launch_encwire(a, items, grid, st, e0, e1));
-    timing_commit(c, slot, QHUFF_KIND_ENCODE);
-    return finish_launch(c, st);
+    return tile_launch(c, n, kWT, encwire_waves_per_block(), c->enc_grid,
+                       out_off, st, [&](const Coord &k, uint32_t grid) -> int {
+        // (mode unused: every item has its own framing)
+        const EncArgs a = enc_args(c, in, in_off, out, out_off, n, 0, k);
+        return timed(c, QHUFF_KIND_ENCODE, "launch_encwire",
+                     [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_encwire(a, items, grid, st, e0, e1);
+        });
+    });
 }
 
 // ---- host helpers --------------------------------------------------------------

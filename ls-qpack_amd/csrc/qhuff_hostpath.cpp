@@ -571,10 +571,8 @@ qhuff::host_batch(qhuff_ctx *c, bool enc, const uint8_t *in, const uint32_t *in_
     // the last shard only)
     if (last_shard)
         out_off[n] = (uint32_t) base;
-    {
-        if ((rc = mirror_error(c)))
-            return rc;
-    }
+    if ((rc = mirror_error(c)))
+        return rc;
     return QHUFF_OK;
 }
 
@@ -602,6 +600,59 @@ qhuff_decode_batch_host(qhuff_ctx *c, const uint8_t *in,
     if (c && c->svc)                      // (see qhuff_encode_batch_host)
         return svc_call(c->svc, false, in, in_off, n, 0, out, out_off, status);
     return host_batch(c, false, in, in_off, n, 0, out, out_off, status);
+}
+
+// ---- one staged round trip ---------------------------------------------------
+//
+// qhuff_decode_stream_host, qhuff_decode_wire_host, qhuff_encode_wire_host
+// (and, the first half, qhuff_xxh32_headers_host): the caller lays its
+// regions out in the stage and makes its device-pointer call on the
+// context's stream between stage_up() and stage_down().  Two
+// synchronisations, the second for output bytes only.
+struct StageIn
+{
+    const void *src;
+    size_t bytes, at;                    // `at`: its offset in the stage
+};
+
+// a stage of `bytes`, the regions copied in, [0, up_end) sent in one copy
+static int
+stage_up(qhuff_ctx *c, size_t bytes, std::initializer_list<StageIn> in,
+         size_t up_end)
+{
+    if (const int rc = ensure_stage(c, bytes))
+        return rc;
+    for (const StageIn &r : in)
+        if (r.bytes)
+            memcpy(c->h_stage + r.at, r.src, r.bytes);
+    HIPCHK(c, hipMemcpyAsync(c->d_stage, c->h_stage, up_end,
+                             hipMemcpyHostToDevice, c->own_stream));
+    return QHUFF_OK;
+}
+
+// the small results [lo, o_out) back (out_off, n + 1 at o_oo, among them),
+// the kernels' error word, then exactly out_off[n] bytes of out
+static int
+stage_down(qhuff_ctx *c, size_t lo, size_t o_oo, size_t o_out, uint32_t n,
+           uint8_t *out, uint32_t *out_off)
+{
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t sk = c->own_stream;
+    HIPCHK(c, hipMemcpyAsync(H + lo, D + lo, o_out - lo, hipMemcpyDeviceToHost,
+                             sk));
+    HIPCHK(c, hipStreamSynchronize(sk));
+    if (const int rc = mirror_error(c))
+        return rc;
+    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
+    if (total)
+    {
+        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
+                                 hipMemcpyDeviceToHost, sk));
+        HIPCHK(c, hipStreamSynchronize(sk));
+        memcpy(out, H + o_out, total);
+    }
+    memcpy(out_off, H + o_oo, 4ull * (n + 1));
+    return QHUFF_OK;
 }
 
 // Host pointers: one staged round trip on the context's stream.  Stage
@@ -633,41 +684,24 @@ qhuff_decode_stream_host(qhuff_ctx *c, const uint8_t *in,
     const size_t o_oo = o_state + up16(2ull * n);
     const size_t o_st = o_oo + up16(4ull * (n + 1));
     const size_t o_out = o_st + up16(n);
-    int rc = ensure_stage(c, o_out + up16(bound));
+    int rc = stage_up(c, o_out + up16(bound),
+                      {{in + a0, in_bytes, 0}, {in_off, 4ull * (n + 1), o_off},
+                       {flags, flags ? n : 0, o_fl},
+                       {state, 2ull * n, o_state}}, o_oo);
     if (rc)
         return rc;
-    uint8_t *H = c->h_stage, *D = c->d_stage;
-    hipStream_t sk = c->own_stream;
-    memcpy(H, in + a0, in_bytes);
-    memcpy(H + o_off, in_off, 4ull * (n + 1));
-    if (flags)
-        memcpy(H + o_fl, flags, n);
-    memcpy(H + o_state, state, 2ull * n);
-    HIPCHK(c, hipMemcpyAsync(D, H, o_oo, hipMemcpyHostToDevice, sk));
+    uint8_t *D = c->d_stage;
     // (the kernel reads the caller's offsets: `in` rebased by -in_off[0])
     rc = qhuff_decode_stream(c, D - a0, (const uint32_t *) (D + o_off), n,
                              (struct qhuff_decode_status *) (D + o_state),
                              flags ? D + o_fl : nullptr, D + o_out,
-                             (uint32_t *) (D + o_oo), D + o_st, sk);
+                             (uint32_t *) (D + o_oo), D + o_st, c->own_stream);
     if (rc)
         return rc;
-    HIPCHK(c, hipMemcpyAsync(H + o_state, D + o_state, o_out - o_state,
-                             hipMemcpyDeviceToHost, sk));
-    HIPCHK(c, hipStreamSynchronize(sk));
-    rc = mirror_error(c);
-    if (rc)
+    if ((rc = stage_down(c, o_state, o_oo, o_out, n, out, out_off)))
         return rc;
-    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
-    if (total)
-    {
-        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
-                                 hipMemcpyDeviceToHost, sk));
-        HIPCHK(c, hipStreamSynchronize(sk));
-        memcpy(out, H + o_out, total);
-    }
-    memcpy(state, H + o_state, 2ull * n);
-    memcpy(out_off, H + o_oo, 4ull * (n + 1));
-    memcpy(status, H + o_st, n);
+    memcpy(state, c->h_stage + o_state, 2ull * n);
+    memcpy(status, c->h_stage + o_st, n);
     return QHUFF_OK;
 }
 
@@ -866,36 +900,21 @@ qhuff_decode_wire_host(qhuff_ctx *c, const uint8_t *buf,
     const size_t o_oo = o_lits + 16ull * n;
     const size_t o_st = o_oo + up16(4ull * (n + 1));
     const size_t o_out = o_st + up16(n);
-    int rc = ensure_stage(c, o_out + up16(bound));
+    int rc = stage_up(c, o_out + up16(bound),
+                      {{buf + lo, span, o_buf}, {lits, 16ull * n, o_lits}},
+                      o_oo);
     if (rc)
         return rc;
-    uint8_t *H = c->h_stage, *D = c->d_stage;
-    hipStream_t sk = c->own_stream;
-    memcpy(H + o_buf, buf + lo, span);
-    memcpy(H + o_lits, lits, 16ull * n);
-    HIPCHK(c, hipMemcpyAsync(D, H, o_oo, hipMemcpyHostToDevice, sk));
+    uint8_t *D = c->d_stage;
     rc = qhuff_decode_wire(c, D + o_buf - lo,
                            (const struct qhuff_literal *) (D + o_lits), n,
                            max_len, D + o_out, (uint32_t *) (D + o_oo),
-                           D + o_st, sk);
+                           D + o_st, c->own_stream);
     if (rc)
         return rc;
-    HIPCHK(c, hipMemcpyAsync(H + o_oo, D + o_oo, o_out - o_oo,
-                             hipMemcpyDeviceToHost, sk));
-    HIPCHK(c, hipStreamSynchronize(sk));
-    rc = mirror_error(c);
-    if (rc)
+    if ((rc = stage_down(c, o_oo, o_oo, o_out, n, out, out_off)))
         return rc;
-    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
-    if (total)
-    {
-        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
-                                 hipMemcpyDeviceToHost, sk));
-        HIPCHK(c, hipStreamSynchronize(sk));
-        memcpy(out, H + o_out, total);
-    }
-    memcpy(out_off, H + o_oo, 4ull * (n + 1));
-    memcpy(status, H + o_st, n);
+    memcpy(status, c->h_stage + o_st, n);
     return QHUFF_OK;
 }
 
@@ -930,36 +949,19 @@ qhuff_encode_wire_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
     const size_t o_it = o_io + up16(4ull * (n + 1));
     const size_t o_oo = o_it + up16(8ull * n);
     const size_t o_out = o_oo + up16(4ull * (n + 1));
-    int rc = ensure_stage(c, o_out + up16(bound));
+    int rc = stage_up(c, o_out + up16(bound),
+                      {{in + a0, bytes, 0}, {in_off, 4ull * (n + 1), o_io},
+                       {items, 8ull * n, o_it}}, o_oo);
     if (rc)
         return rc;
-    uint8_t *H = c->h_stage, *D = c->d_stage;
-    hipStream_t sk = c->own_stream;
-    memcpy(H, in + a0, bytes);
-    memcpy(H + o_io, in_off, 4ull * (n + 1));
-    memcpy(H + o_it, items, 8ull * n);
-    HIPCHK(c, hipMemcpyAsync(D, H, o_oo, hipMemcpyHostToDevice, sk));
+    uint8_t *D = c->d_stage;
     rc = qhuff_encode_wire(c, D - a0, (const uint32_t *) (D + o_io),
                            (const struct qhuff_item *) (D + o_it), n,
-                           D + o_out, (uint32_t *) (D + o_oo), sk);
+                           D + o_out, (uint32_t *) (D + o_oo),
+                           c->own_stream);
     if (rc)
         return rc;
-    HIPCHK(c, hipMemcpyAsync(H + o_oo, D + o_oo, o_out - o_oo,
-                             hipMemcpyDeviceToHost, sk));
-    HIPCHK(c, hipStreamSynchronize(sk));
-    rc = mirror_error(c);
-    if (rc)
-        return rc;
-    const uint32_t total = ((const uint32_t *) (H + o_oo))[n];
-    if (total)
-    {
-        HIPCHK(c, hipMemcpyAsync(H + o_out, D + o_out, total,
-                                 hipMemcpyDeviceToHost, sk));
-        HIPCHK(c, hipStreamSynchronize(sk));
-        memcpy(out, H + o_out, total);
-    }
-    memcpy(out_off, H + o_oo, 4ull * (n + 1));
-    return QHUFF_OK;
+    return stage_down(c, o_oo, o_oo, o_out, n, out, out_off);
 }
 
 // ---- header hashing, host buffers ----------------------------------------------
@@ -982,25 +984,22 @@ qhuff_xxh32_headers_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
     const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
     const size_t o_off = up16(bytes), o_h1 = o_off + up16(4ull * (2ull * n + 1));
     const size_t o_h2 = o_h1 + up16(4ull * n), total = o_h2 + up16(4ull * n);
-    int rc = ensure_stage(c, total);
+    int rc = stage_up(c, total, {{in + a0, bytes, 0},
+                                 {off, 4ull * (2ull * n + 1), o_off}}, o_h1);
     if (rc)
         return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
     hipStream_t st = c->own_stream;
-    memcpy(c->h_stage, in + a0, bytes);
-    memcpy(c->h_stage + o_off, off, 4ull * (2ull * n + 1));
-    HIPCHK(c, hipMemcpyAsync(c->d_stage, c->h_stage, o_h1,
-                             hipMemcpyHostToDevice, st));
-    rc = qhuff_xxh32_headers(c, c->d_stage - a0,
-                             (const uint32_t *) (c->d_stage + o_off), n, seed,
-                             (uint32_t *) (c->d_stage + o_h1),
-                             (uint32_t *) (c->d_stage + o_h2), st);
+    rc = qhuff_xxh32_headers(c, D - a0, (const uint32_t *) (D + o_off), n,
+                             seed, (uint32_t *) (D + o_h1),
+                             (uint32_t *) (D + o_h2), st);
     if (rc)
         return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_stage + o_h1, c->d_stage + o_h1,
-                             total - o_h1, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(H + o_h1, D + o_h1, total - o_h1,
+                             hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    memcpy(name_hash, c->h_stage + o_h1, 4ull * n);
-    memcpy(nameval_hash, c->h_stage + o_h2, 4ull * n);
+    memcpy(name_hash, H + o_h1, 4ull * n);
+    memcpy(nameval_hash, H + o_h2, 4ull * n);
     return QHUFF_OK;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include "../../include/qhuff.h"
@@ -165,8 +166,23 @@ glb(T *p)
     return (QH_GLB T *) p;
 }
 
-// ev0 / ev1 non-null: the launch records its own start / stop time in them
-// (hipExtLaunchKernelGGL: the dispatch's timestamps, no extra queue packets)
+// One launch of `kernel` over `grid` workgroups of `block` threads (the
+// kernel files' launch_* functions).  ev0 / ev1 non-null: the launch records
+// its own start / stop time in them (the dispatch's timestamps, no extra
+// queue packets).
+template <class K, class A>
+static inline hipError_t
+launch_kernel(K kernel, uint32_t grid, uint32_t block, hipStream_t st,
+              hipEvent_t ev0, hipEvent_t ev1, const A &args)
+{
+    if (ev0)
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, ev0,
+                              ev1, 0, args);
+    else
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, args);
+    return hipGetLastError();
+}
+
 // full: the kernel variant with big-tile slots and cooperative long strings
 // (qhuff_pipeline.h); the lean one is the default (qhuff_host.cpp)
 hipError_t launch_encode(const EncArgs &a, uint32_t grid, hipStream_t st,
@@ -179,18 +195,15 @@ hipError_t launch_decode(const DecArgs &a, uint32_t grid, hipStream_t st,
                          bool keep = false, bool full = false);
 hipError_t launch_stream(const StreamArgs &a, uint32_t grid, hipStream_t st,
                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-hipError_t stream_occupancy(int *blocks_per_cu);
 int stream_waves_per_block();
 hipError_t launch_wire(const WireArgs &a, uint32_t grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-hipError_t wire_occupancy(int *blocks_per_cu);
 int wire_waves_per_block();
 // items encoded in one launch (qhuff_encwire.hip): the encode arguments
 // (mode unused: every item has its own framing) and the n items
 hipError_t launch_encwire(const EncArgs &a, const ::qhuff_item *items,
                           uint32_t grid, hipStream_t st,
                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-hipError_t encwire_occupancy(int *blocks_per_cu);
 int encwire_waves_per_block();
 hipError_t launch_hash(const HashArgs &a, uint32_t max_grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);

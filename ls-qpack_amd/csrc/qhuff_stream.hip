@@ -19,8 +19,6 @@
 // tiles past the 3 KB stages are coded out of line, each chunk by its lane.
 #include "qhuff_stream_impl.h"
 
-#include <hip/hip_ext.h>
-
 #ifndef QH_DEC_PER
 #define QH_DEC_PER 2
 #endif
@@ -34,18 +32,15 @@ qhuff_stream_kernel(StreamArgs s)
     QH_LDS StreamSmem *sm = (QH_LDS StreamSmem *) &smem;
     const DecArgs &a = s.d;
     const int tid = threadIdx.x;
-    Tickets tk;
-    tk.init();
-    // the prologue of qhuff_decode_kernel: ticket claims, then the table
-    // loads, stored once the first offsets loads are out
-    const uint32_t cb = claim_block_issue(a.c, tk, QH_DEC_PER);
-    DecTableLoads tl;
-    tl.issue(a.win, a.sorted, a.long2, tid);
+    // (ticket claims, then the table loads -- the nodes among them --
+    // stored once the first offsets loads are out)
     static_assert(kNodes <= 64 * kWaves, "one node per thread");
-    const uint32_t nd = glb(s.nodes)[tid < kNodes ? tid : 0];
-    claim_block_store(a.c, cb, &sm->tk, QH_DEC_PER);
-    clear_next_launch(a.c);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    const auto p = dec_prologue<QH_DEC_PER>(a, sm, tid, [&](int t) {
+        return glb(s.nodes)[t < kNodes ? t : 0];
+    });
+    const Tickets &tk = p.tk;
+    const DecTableLoads tl = p.tl;
+    const uint32_t nd = p.own;
     StreamPolicy pol{a.in, sm,
                      &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)],
                      StreamIo{s.state, s.flags}, 0, StreamEnd{0, 0, 0}};
@@ -65,21 +60,8 @@ hipError_t
 launch_stream(const StreamArgs &a, uint32_t grid, hipStream_t st,
               hipEvent_t ev0, hipEvent_t ev1)
 {
-    if (ev0)
-        hipExtLaunchKernelGGL(qhuff_stream_kernel, dim3(grid),
-                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
-    else
-        hipLaunchKernelGGL(qhuff_stream_kernel, dim3(grid), dim3(64 * kWaves),
-                           0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t
-stream_occupancy(int *blocks_per_cu)
-{
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        blocks_per_cu, reinterpret_cast<const void *>(qhuff_stream_kernel),
-        64 * kWaves, 0);
+    return launch_kernel(qhuff_stream_kernel, grid, 64 * kWaves, st, ev0, ev1,
+                         a);
 }
 
 int

@@ -21,8 +21,6 @@
 // coded out of line, each literal by its lane.
 #include "qhuff_wire_impl.h"
 
-#include <hip/hip_ext.h>
-
 #ifndef QH_DEC_PER
 #define QH_DEC_PER 2
 #endif
@@ -36,16 +34,11 @@ qhuff_wire_kernel(WireArgs w)
     QH_LDS DecSmem *sm = (QH_LDS DecSmem *) &smem;
     const DecArgs &a = w.d;
     const int tid = threadIdx.x;
-    Tickets tk;
-    tk.init();
-    // the prologue of qhuff_decode_kernel: ticket claims, then the table
-    // loads, stored once the first descriptor loads are out
-    const uint32_t cb = claim_block_issue(a.c, tk, QH_DEC_PER);
-    DecTableLoads tl;
-    tl.issue(a.win, a.sorted, a.long2, tid);
-    claim_block_store(a.c, cb, &sm->tk, QH_DEC_PER);
-    clear_next_launch(a.c);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // (ticket claims, then the table loads, stored once the first
+    // descriptor loads are out)
+    const auto p = dec_prologue<QH_DEC_PER>(a, sm, tid);
+    const Tickets &tk = p.tk;
+    const DecTableLoads tl = p.tl;
     WirePolicy pol{a.in, sm, &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)],
                    WireLimit{(const ::qhuff_literal *) a.in_off, w.max_len},
                    0};
@@ -63,21 +56,8 @@ hipError_t
 launch_wire(const WireArgs &a, uint32_t grid, hipStream_t st, hipEvent_t ev0,
             hipEvent_t ev1)
 {
-    if (ev0)
-        hipExtLaunchKernelGGL(qhuff_wire_kernel, dim3(grid),
-                              dim3(64 * kWaves), 0, st, ev0, ev1, 0, a);
-    else
-        hipLaunchKernelGGL(qhuff_wire_kernel, dim3(grid), dim3(64 * kWaves),
-                           0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t
-wire_occupancy(int *blocks_per_cu)
-{
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        blocks_per_cu, reinterpret_cast<const void *>(qhuff_wire_kernel),
-        64 * kWaves, 0);
+    return launch_kernel(qhuff_wire_kernel, grid, 64 * kWaves, st, ev0, ev1,
+                         a);
 }
 
 int
