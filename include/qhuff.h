@@ -172,6 +172,26 @@ int qhuff_decode_batch_host(qhuff_ctx *ctx, const uint8_t *in,
 int qhuff_host_register(void *ptr, size_t bytes);
 int qhuff_host_unregister(void *ptr);
 
+/* Diagnostic, host-only: the string ranges qhuff_*_batch_host cuts this
+ * batch into (in_off: n + 1 host offsets; enc 0: decode, else encode with
+ * `mode`).  One chunk per 2^chunk_shift bytes of input, at most 16 and at
+ * most one a string; chunk i is the strings [cut[i], cut[i + 1]), with
+ * cut[i] = n * i / K.
+ * chunk_shift 0: the process's own (QHUFF_HOST_CHUNK_SHIFT, default 23); a
+ * value outside 16..30 counts as 23, as in the environment.
+ * cut: K + 1 entries (room for 17).  *small (may be null): 1 when the call
+ * takes the one-synchronisation path (one chunk whose output bound, rounded
+ * up to 16, is at most 4 MB; registered outputs are then staged).  Returns K
+ * (>= 1), QHUFF_EINVAL (a null pointer, a bad mode, in_off[n] < in_off[0])
+ * or QHUFF_ERANGE (the chunks' bounds together pass 2^32 - 1).  A shard of a
+ * *_host_multi call is cut the same way from its own offsets.  Host
+ * arithmetic only: no context, no device call.  QHUFF_FEATURE_HOST_CHUNKS
+ * and the symbol announce it (the ABI version is unchanged). */
+#define QHUFF_FEATURE_HOST_CHUNKS 1
+int qhuff_host_chunks(int enc, unsigned mode, const uint32_t *in_off,
+                      uint32_t n, unsigned chunk_shift, uint32_t *cut,
+                      uint32_t *small);
+
 /* ---- low-latency service ----------------------------------------------
  * The reference codes one literal per call, a few dozen per header block
  * (lsqpack.c:3718, 3795, 4714, 4824, 4908 decode; 1983-2119 encode).  A

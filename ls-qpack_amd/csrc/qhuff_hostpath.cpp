@@ -309,6 +309,80 @@ qhuff_host_unregister(void *ptr)
     return QHUFF_EINVAL;
 }
 
+// ---- the chunk plan of the host path -----------------------------------------
+//
+// Chunks of >= 2^shift bytes of input (QHUFF_HOST_CHUNK_SHIFT, 16..30;
+// default 8 MB: measured on MI355X, 1M strings, 8 copy threads -- 2 MB
+// chunks 2.9 / 2.7 ms enc / dec, 4 MB 2.2 / 2.0, 8 MB 1.8 / 1.7, 16 MB
+// 1.9 / 2.3; tools/host_path_probe.py), at most kMaxChunks and at most one
+// a string.  Chunk i is the strings [cut[i], cut[i + 1]); its output region
+// in the stage starts at ob[i] and holds its own bound, rounded up to 16.
+struct ChunkPlan
+{
+    unsigned K;
+    uint32_t cut[kMaxChunks + 1];
+    uint64_t ob[kMaxChunks + 1];                 // out region starts
+    // a small batch brings its whole output bound back right behind the
+    // kernel: one synchronisation instead of two (latency, not bandwidth)
+    bool small;
+};
+
+static inline unsigned
+chunk_shift_of(unsigned v)
+{
+    return v >= 16 && v <= 30 ? v : 23u;
+}
+
+// the process's own shift, read once
+static unsigned
+env_chunk_shift()
+{
+    static const unsigned shift = [] {
+        const char *e = getenv("QHUFF_HOST_CHUNK_SHIFT");
+        return chunk_shift_of(e ? (unsigned) strtoul(e, nullptr, 0) : 23u);
+    }();
+    return shift;
+}
+
+static void
+chunk_plan(bool enc, unsigned mode, const uint32_t *in_off, uint32_t n,
+           unsigned shift, ChunkPlan &p)
+{
+    const uint64_t in_bytes = (uint64_t) in_off[n] - in_off[0];
+    unsigned K = (unsigned) (in_bytes >> shift);
+    K = K < 1 ? 1 : (K > kMaxChunks ? kMaxChunks : K);
+    if (K > n)
+        K = n ? n : 1;
+    p.K = K;
+    p.ob[0] = 0;
+    for (unsigned i = 0; i <= K; ++i)
+        p.cut[i] = (uint32_t) ((uint64_t) n * i / K);
+    for (unsigned i = 0; i < K; ++i)
+    {
+        const uint32_t s0 = p.cut[i], s1 = p.cut[i + 1];
+        const uint64_t b = (uint64_t) in_off[s1] - in_off[s0];
+        p.ob[i + 1] = p.ob[i] + up16(bound_of(enc, b, s1 - s0, mode));
+    }
+    p.small = K == 1 && p.ob[1] <= (4u << 20);
+}
+
+extern "C" int
+qhuff_host_chunks(int enc, unsigned mode, const uint32_t *in_off, uint32_t n,
+                  unsigned chunk_shift, uint32_t *cut, uint32_t *small)
+{
+    if (!in_off || !cut || (enc && !mode_ok(mode)) || in_off[n] < in_off[0])
+        return QHUFF_EINVAL;
+    ChunkPlan p;
+    chunk_plan(enc != 0, mode, in_off, n,
+               chunk_shift ? chunk_shift_of(chunk_shift) : env_chunk_shift(), p);
+    if (p.ob[p.K] > 0xffffffffull)
+        return QHUFF_ERANGE;
+    memcpy(cut, p.cut, 4ull * (p.K + 1));
+    if (small)
+        *small = p.small;
+    return (int) p.K;
+}
+
 // The PCIe-inclusive path as a chunked pipeline.  The batch is cut into K
 // string ranges; per chunk: pinned staging copy (copy workers) -> H2D on the
 // upload stream -> kernel on the context stream (its out_off / status come
@@ -339,30 +413,12 @@ qhuff::host_batch(qhuff_ctx *c, bool enc, const uint8_t *in, const uint32_t *in_
     if (rc)
         return rc;
     const uint64_t a0 = in_off[0], in_bytes = (uint64_t) in_off[n] - a0;
-    // chunks of >= 2^chunk_shift bytes of input (QHUFF_HOST_CHUNK_SHIFT;
-    // default 8 MB: measured on MI355X, 1M strings, 8 copy threads -- 2 MB
-    // chunks 2.9 / 2.7 ms enc / dec, 4 MB 2.2 / 2.0, 8 MB 1.8 / 1.7, 16 MB
-    // 1.9 / 2.3; tools/host_path_probe.py), at most kMaxChunks
-    static const unsigned chunk_shift = [] {
-        const char *e = getenv("QHUFF_HOST_CHUNK_SHIFT");
-        const unsigned v = e ? (unsigned) strtoul(e, nullptr, 0) : 23u;
-        return v >= 16 && v <= 30 ? v : 23u;
-    }();
-    unsigned K = (unsigned) (in_bytes >> chunk_shift);
-    K = K < 1 ? 1 : (K > kMaxChunks ? kMaxChunks : K);
-    if (K > n)
-        K = n ? n : 1;
-    uint32_t cut[kMaxChunks + 1];
-    uint64_t ob[kMaxChunks + 1];                 // out region starts
-    ob[0] = 0;
-    for (unsigned i = 0; i <= K; ++i)
-        cut[i] = (uint32_t) ((uint64_t) n * i / K);
-    for (unsigned i = 0; i < K; ++i)
-    {
-        const uint32_t s0 = cut[i], s1 = cut[i + 1];
-        const uint64_t b = (uint64_t) in_off[s1] - in_off[s0];
-        ob[i + 1] = ob[i] + up16(bound_of(enc, b, s1 - s0, mode));
-    }
+    // (the plan qhuff_host_chunks reports)
+    ChunkPlan plan;
+    chunk_plan(enc, mode, in_off, n, env_chunk_shift(), plan);
+    const unsigned K = plan.K;
+    const uint32_t *cut = plan.cut;
+    const uint64_t *ob = plan.ob;
     if (ob[K] > 0xffffffffull)
         return QHUFF_ERANGE;
     const size_t o_in = 0, o_off = up16(in_bytes);
@@ -379,9 +435,7 @@ qhuff::host_batch(qhuff_ctx *c, bool enc, const uint8_t *in, const uint32_t *in_
     uint32_t tot[kMaxChunks];
     uint64_t obase[kMaxChunks];                  // chunk i's output start
     uint64_t fbase = 0;                          // (relative to the call's)
-    // a small batch brings its whole output bound back right behind the
-    // kernel: one synchronisation instead of two (latency, not bandwidth)
-    const bool small = K == 1 && ob[1] <= (4u << 20);
+    const bool small = plan.small;
     // caller buffers registered for DMA (qhuff_host_register): transferred
     // directly, no staging copy
     const bool din = host_registered(in + a0, in_bytes)

@@ -42,6 +42,7 @@ EXPORTS = (
     "qhuff_dec_int", "qhuff_encode_batch_host_multi",
     "qhuff_decode_batch_host_multi", "qhuff_encode_batch_multi",
     "qhuff_decode_batch_multi", "qhuff_host_register", "qhuff_host_unregister",
+    "qhuff_host_chunks",
     "qhuff_decode_stream_bound", "qhuff_decode_stream",
     "qhuff_decode_stream_host",
     "qhuff_literals_check", "qhuff_decode_wire", "qhuff_decode_wire_host",
@@ -263,6 +264,9 @@ def lib():
         L.qhuff_host_register.argtypes = [vp, C.c_size_t]
         L.qhuff_host_unregister.restype = C.c_int
         L.qhuff_host_unregister.argtypes = [vp]
+        L.qhuff_host_chunks.restype = C.c_int
+        L.qhuff_host_chunks.argtypes = [C.c_int, C.c_uint, u32p, C.c_uint32,
+                                        C.c_uint, u32p, C.POINTER(C.c_uint32)]
         L.qhuff_decode_stream_bound.restype = C.c_uint64
         L.qhuff_decode_stream_bound.argtypes = [C.c_uint64, C.c_uint32]
         L.qhuff_decode_stream.restype = C.c_int
@@ -341,6 +345,23 @@ def svc_pieces(in_off, max_pieces=None):
     if rc:
         raise QhuffError("qhuff_svc_pieces: %d (%d pieces)" % (rc, k.value))
     return [int(x) for x in cuts[:k.value + 1]]
+
+
+def host_chunks(in_off, enc=True, mode=ENC_PAYLOAD, chunk_shift=0):
+    """qhuff_host_chunks: (cut, small) -- the K + 1 string indices at which
+    the host-memory calls cut a batch of these offsets into chunks, and
+    whether the call takes the one-synchronisation path.  chunk_shift 0: the
+    process's own (QHUFF_HOST_CHUNK_SHIFT)."""
+    import numpy as np
+    in_off = np.ascontiguousarray(in_off, dtype=np.uint32)
+    cut = np.zeros(17, dtype=np.uint32)
+    small = C.c_uint32()
+    k = lib().qhuff_host_chunks(int(bool(enc)), mode if enc else 0,
+                                _np_ptr(in_off), len(in_off) - 1, chunk_shift,
+                                _np_ptr(cut), C.byref(small))
+    if k < 1:
+        raise QhuffError("qhuff_host_chunks: %d" % k)
+    return [int(x) for x in cut[:k + 1]], bool(small.value)
 
 
 def batch_needs_full(in_off):
