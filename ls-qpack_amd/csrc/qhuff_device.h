@@ -692,7 +692,11 @@ struct LookBack
         if (tile == f0 + in_super - 1)
             publish_super(c, kFlagInc, excl + total);
 #ifdef QHUFF_PROFILE
-        spins_seen = spins1 | ((spins - spins1) << 12) | (extra << 24);
+        // (12 bits a count, saturated: a wait behind a slow tile passes
+        // 4,096 polls, and the carry read as windows polled)
+        const uint32_t sp1 = spins1 < 0xfffu ? spins1 : 0xfffu;
+        const uint32_t sp2 = spins - spins1 < 0xfffu ? spins - spins1 : 0xfffu;
+        spins_seen = sp1 | (sp2 << 12) | (extra << 24);
 #else
         (void) spins1;
         (void) extra;

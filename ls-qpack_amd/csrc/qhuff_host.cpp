@@ -322,6 +322,10 @@ qhuff_open(int device, qhuff_ctx **ctx_out)
         return rc;
     }
     c->epoch = 0;
+    // test knob: the epoch the context starts behind, so that a test can
+    // open one a few launches before the 22-bit wrap (prepare_launch)
+    if (const char *e0 = getenv("QHUFF_EPOCH0"))
+        c->epoch = (uint32_t) strtoul(e0, nullptr, 0) & kEpochMask;
     c->hint[0] = c->hint[1] = -1;
     c->max_banks = kPoolBanks;
     if (const char *sb = getenv("QHUFF_SLOT_BANKS"))

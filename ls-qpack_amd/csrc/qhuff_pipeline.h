@@ -734,7 +734,18 @@ tile_pipeline(P &pol, const Coord &c, const Tickets &tk, uint32_t t0,
 #pragma unroll
     for (int i = 0; i < D; ++i)
         if (pend[i].valid)
+        {
             flush_at(i, ld[i], ~0u);
+#ifdef QHUFF_PROFILE
+            // (profiling) the drain's look-backs, where a wave's last tiles
+            // and every tile of a wave of at most kDepth tiles resolve: the
+            // counts of slot 8, the tile above them (values, not stamps:
+            // tools/profile_phases.py keeps iteration 14 out of its means)
+            if (i < 3)
+                prof_value(c, kProfIters - 2, 9 + i,
+                           ld[i].spins_seen | ((uint64_t) pend[i].tile << 32));
+#endif
+        }
 #ifdef QHUFF_PROFILE
     wait_vm_all();
     prof_stamp(c, kProfIters - 2, 7);        // (profiling) drain end

@@ -85,6 +85,11 @@ def report(tag, p):
         print("  re-polls: tile window mean %.2f (>0 in %.1f%%) | super windows mean %.2f (>0 in %.1f%%) | windows past two mean %.2f (>0 in %.1f%%)"
               % (w1.mean(), 100.0 * (w1 > 0).mean(), w2.mean(),
                  100.0 * (w2 > 0).mean(), w3.mean(), 100.0 * (w3 > 0).mean()))
+    # (iteration 14 belongs to the drain: slots 6-8 its stamps, slots 9-11
+    # the re-poll counts of its look-backs with the tile in the upper half,
+    # qhuff_pipeline.h -- no timestamps, so it stays out of the means below)
+    live = live.copy()
+    live[:, ITERS - 2] = False
     ok = live & (p[:, :, 3] != 0) & (p[:, :, 9] != 0) & (p[:, :, 4] != 0)
     if ok.any():
         a = (p[:, :, 9] - p[:, :, 3])[ok]
