@@ -678,7 +678,9 @@ int qhuff_device_error(qhuff_ctx *ctx);
 
 /* Diagnostic: in a QHUFF_PROFILE build (libqhuff_prof.so) copy up to
  * max_words per-wave phase stamps of the last launch into dst and return
- * the number available; 0 in normal builds.  Synchronous. */
+ * the number available; 0 in normal builds.  In a QH_PATH_TRACE build
+ * (libqhuff_trace.so) the words are the last tile launch's path records,
+ * 8 per tile in tile order.  Synchronous. */
 uint64_t qhuff_profile_read(qhuff_ctx *ctx, uint64_t *dst, uint64_t max_words);
 
 /* Launch timing.  With timing on, every encode / decode / hash launch of

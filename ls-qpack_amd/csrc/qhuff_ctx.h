@@ -68,8 +68,10 @@ struct qhuff_ctx
                                          // (host_hint), or -1: full
     int kernels;                         // QHUFF_KERNELS: 0 auto, 1 lean,
                                          // 2 full
-    unsigned long long *prof;            // QHUFF_PROFILE builds: stamp buffer
-    size_t prof_words;
+    unsigned long long *prof;            // QHUFF_PROFILE builds: stamp buffer;
+                                         // QH_PATH_TRACE builds: tile records
+    size_t prof_words;                   // words of the last launch
+    size_t prof_cap;                     // words allocated (path trace)
     uint32_t epoch;
     // host-path staging
     uint8_t *h_stage;                    // pinned

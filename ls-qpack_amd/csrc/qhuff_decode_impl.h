@@ -807,7 +807,11 @@ coop_decode(const QH_LDS uint32_t *src, uint64_t coop, uint32_t rs,
             uint32_t re, uint32_t slot, QH_LDS uint8_t *arena,
             QH_LDS uint8_t *sink,
             const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_sorted,
-            const Coord *pc = nullptr)
+            const Coord *pc = nullptr
+#ifdef QH_PATH_TRACE
+            , PathTrace *tr = nullptr
+#endif
+            )
 {
     // (profiling) the wave's last cooperative call: iteration 15, slots 4-9
     auto stamp = [&](int k) {
@@ -892,6 +896,10 @@ coop_decode(const QH_LDS uint32_t *src, uint64_t coop, uint32_t rs,
         const uint32_t tE = (q >= 1 && !pm) ? px : E;
         redo = cl & (tE != cs);
         cs = cl ? tE : cs;
+#ifdef QH_PATH_TRACE
+        if (tr && rounds >= 64)              // (the guard below: recorded)
+            tr->first_call(S, rounds + 1);
+#endif
         if (++rounds > 64)                   // (cannot happen: segment q's
             return mine ? -1 : 0;            // exit is fixed after q rounds)
     }
@@ -899,6 +907,10 @@ coop_decode(const QH_LDS uint32_t *src, uint64_t coop, uint32_t rs,
 #ifdef QHUFF_PROFILE
     if (pc)
         prof_value(*pc, kProfIters - 1, 9, rounds);
+#endif
+#ifdef QH_PATH_TRACE
+    if (tr)
+        tr->first_call(S, rounds);
 #endif
     // symbols of each segment, offsets within the string
     const uint32_t kp = all_lanes(wave_shr1(K));
@@ -1125,7 +1137,11 @@ template <bool Keep, class SM>
 __device__ __forceinline__ bool
 dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
               uint32_t cnt, TileOffs to, Span sp, uint32_t &sz, uint32_t &st,
-              uint32_t slot0, uint8_t *dst);
+              uint32_t slot0, uint8_t *dst
+#ifdef QH_PATH_TRACE
+              , PathTrace &tr
+#endif
+              );
 
 // the decode side of the wave pipeline (qhuff_pipeline.h, qhuff_service.hip);
 // SM: the workgroup's LDS (win, sorted).  Keep (the kernel the per-string
@@ -1155,6 +1171,9 @@ struct DecPolicyT
     uint64_t coop = 0;               // strings decoded by the whole wave
 #ifdef QHUFF_PROFILE
     const Coord *pc = nullptr;       // (profiling) stamps of coop_decode
+#endif
+#ifdef QH_PATH_TRACE
+    PathTrace tr;                    // (diagnostic) the current tile's paths
 #endif
 
     __device__ __forceinline__ void stage_in(const Chunks<kNch> &ch,
@@ -1198,6 +1217,11 @@ struct DecPolicyT
         coop = __builtin_amdgcn_ballot_w64(cand);
         if (__builtin_popcountll(coop) > 48)
             coop = 0;
+#ifdef QH_PATH_TRACE
+        tr.units += 1;
+        tr.var += fixed ? 0u : 1u;
+        tr.coop |= coop;
+#endif
         const bool mine = (coop >> lane) & 1;
         int r = 0;
         if (valid)
@@ -1230,10 +1254,15 @@ struct DecPolicyT
             wv->arena + kArenaBytes - kCoopDummy, sm->win, sm->sorted
 #ifdef QHUFF_PROFILE
             , pc
+#elif defined(QH_PATH_TRACE)
+            , nullptr, &tr
 #endif
             );
         r = rc;
         const uint64_t fail = __builtin_amdgcn_ballot_w64(mine & (rc < 0));
+#ifdef QH_PATH_TRACE
+        tr.fail |= fail;
+#endif
 #ifdef QH_COOP_DEBUG
         if (fail)
         {
@@ -1305,7 +1334,11 @@ struct DecPolicyT
         if (kCoop && sp.staged && coop)
             coop_phase(to, 0, cnt, sp, &sz, &st);
 #endif
-        return dec_big_sizes<Keep>(in, sm, wv, cnt, to, sp, sz, st, slot0, dst);
+        return dec_big_sizes<Keep>(in, sm, wv, cnt, to, sp, sz, st, slot0, dst
+#ifdef QH_PATH_TRACE
+                                   , tr
+#endif
+                                   );
     }
     // a big tile whose output does not fit a slot (qhuff_pipeline.h), after
     // the pending tiles are flushed: base from the look-back
@@ -1359,7 +1392,11 @@ template <bool Keep, class SM>
 __device__ __forceinline__ bool
 dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
               uint32_t cnt, TileOffs to, Span sp, uint32_t &sz, uint32_t &st,
-              uint32_t slot0, uint8_t *dst)
+              uint32_t slot0, uint8_t *dst
+#ifdef QH_PATH_TRACE
+              , PathTrace &tr
+#endif
+              )
 {
     using P = DecPolicyT<SM, Keep, true>;
     P pol{in, sm, wv, 0};
@@ -1431,6 +1468,9 @@ dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
                 sz = r >= 0 ? (uint32_t) r : Keep ? (uint32_t) (-1 - r) : 0u;
                 st = r < 0 ? QHUFF_DEC_ERROR : QHUFF_DEC_OK;
             }
+#ifdef QH_PATH_TRACE
+            tr.lone += 1;
+#endif
             fits = w;
             run += read_lane(sz, i0);
             i0 += 1;
@@ -1453,6 +1493,9 @@ dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
         wave_sync();
         i0 += k;
     }
+#ifdef QH_PATH_TRACE
+    tr.add(pol.tr);                          // (the units' counts)
+#endif
     return fits;
 }
 

@@ -79,7 +79,8 @@ constexpr uint32_t kTickStride = 64;
 
 struct Coord
 {
-    unsigned long long *prof;               // QHUFF_PROFILE builds: stamps
+    unsigned long long *prof;               // QHUFF_PROFILE builds: stamps;
+                                            // QH_PATH_TRACE: tile records
     unsigned long long *flags;              // per-tile look-back flags
     unsigned long long *sflags;             // per-super-tile flags
     unsigned long long *sacc;               // super accumulators [2][cap_super],
@@ -380,6 +381,80 @@ prof_stamp(const Coord &c, uint32_t it, int ph)
     (void) ph;
 #endif
 }
+
+// ---- path trace (QH_PATH_TRACE builds only) ------------------------------
+// One record of kTraceWords u64 per tile, at prof[tile * kTraceWords]
+// (sized and zeroed per launch by the host, read with qhuff_profile_read):
+// which of each pair of equivalent paths the tile took.  The policies count
+// into their PathTrace member while they code a tile; tile_pipeline writes
+// the record at the end of the tile's iteration, after every decision, and
+// clears the counts.  Nothing on the device reads a record and no decision
+// depends on the define ("The path trace").
+//   w0  bit 0 written, bit 1 sp_cur.staged, bits 3:2 exit (1 fast: from the
+//       out stage, 2 slot: bigslot != 0, 3 slow: P::slow_tile ran)
+//   w1  [15:0] staged units coded (codec / codec_range calls), [31:16] lone
+//       strings walked in global memory, [47:32] units in the variable
+//       arena, [63:48] units coded from the dense stream
+//   w2  lanes flagged cooperative (decode), OR-ed over the units
+//   w3  lanes whose cooperative result was rejected and decoded again by
+//       the lane (coop_phase's fail)
+//   w4  the first coop_decode call of the tile: [31:0] S, [47:32] trips of
+//       its B loop, bit 63 set once there was one
+//   w5  lanes whose payload the whole wave copied (encode: lm in emit)
+#if defined(QH_PATH_TRACE) && defined(QHUFF_PROFILE)
+#error "QH_PATH_TRACE and QHUFF_PROFILE share Coord::prof: build one of them"
+#endif
+#ifdef QH_PATH_TRACE
+constexpr uint32_t kTraceWords = 8;
+struct PathTrace
+{
+    uint32_t units = 0, lone = 0, var = 0, dense = 0;
+    uint32_t S = 0, rounds = 0, first = 0;
+    uint64_t coop = 0, fail = 0, enc_coop = 0;
+    // coop_decode's S and B trips: the first call of the tile is kept
+    __device__ __forceinline__ void first_call(uint32_t seg, uint32_t trips)
+    {
+        if (!first)
+        {
+            S = seg;
+            rounds = trips;
+            first = 1;
+        }
+    }
+    // the counts of a big tile's units (dec_big_sizes, enc_big_sizes)
+    __device__ __forceinline__ void add(const PathTrace &o)
+    {
+        units += o.units;
+        lone += o.lone;
+        var += o.var;
+        dense += o.dense;
+        if (o.first)
+            first_call(o.S, o.rounds);
+        coop |= o.coop;
+        fail |= o.fail;
+        enc_coop |= o.enc_coop;
+    }
+    // exit: 1 fast, 2 slot, 3 slow (every value wave-uniform; lane 0 stores)
+    __device__ __forceinline__ void write(const Coord &c, uint32_t tile,
+                                          bool staged, uint32_t exit) const
+    {
+        if (c.prof && tile < c.n_tiles && (threadIdx.x & 63) == 0)
+        {
+            QH_GLB unsigned long long *r =
+                (QH_GLB unsigned long long *) c.prof + (uint64_t) tile * kTraceWords;
+            r[0] = 1u | (staged ? 2u : 0u) | (exit << 2);
+            r[1] = (uint64_t) (units & 0xffff) | (uint64_t) (lone & 0xffff) << 16
+                 | (uint64_t) (var & 0xffff) << 32
+                 | (uint64_t) (dense & 0xffff) << 48;
+            r[2] = coop;
+            r[3] = fail;
+            r[4] = (uint64_t) S | (uint64_t) (rounds & 0xffff) << 32
+                 | (uint64_t) first << 63;
+            r[5] = enc_coop;
+        }
+    }
+};
+#endif
 
 // ---- tile offsets ------------------------------------------------------
 

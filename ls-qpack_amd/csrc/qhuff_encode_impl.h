@@ -873,7 +873,11 @@ template <class SM>
 __device__ __forceinline__ bool
 enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
               QH_LDS EncWave *wv, uint32_t cnt, TileOffs to, Span sp,
-              uint32_t &sz, uint8_t *dst);
+              uint32_t &sz, uint8_t *dst
+#ifdef QH_PATH_TRACE
+              , PathTrace &tr
+#endif
+              );
 
 // the encode side of the wave pipeline (qhuff_pipeline.h, qhuff_service.hip);
 // SM: the workgroup's LDS (enc, mt, len)
@@ -900,6 +904,9 @@ struct EncPolicyT
     uint32_t ds, bits;               // its range of the dense stream
     EncSize z;
     uint32_t dense;                  // wave-uniform: tile from the dense stream
+#ifdef QH_PATH_TRACE
+    PathTrace tr;                    // (diagnostic) the current tile's paths
+#endif
 
     // staged tile: chunks into the LDS stage
     __device__ __forceinline__ void stage_in(const Chunks<kChunks> &ch,
@@ -957,6 +964,10 @@ struct EncPolicyT
             bits = se - ds;
             dense = read_lane(se, cnt - 1) + 64 <= kDenseBits;
         }
+#ifdef QH_PATH_TRACE
+        tr.units += 1;
+        tr.dense += dense ? 1u : 0u;
+#endif
         if (valid)
             z = dense ? size_from_bits(mode, bits, re - rs)
                       : size_string(mode, EncLds{wv->in}, rs, re, sm->len);
@@ -981,6 +992,9 @@ struct EncPolicyT
             const bool lc = Full && QH_ENC_COOP && (sz != 0) & z.huff
                           & (bits > kEncCoopBits);
             const uint64_t lm = __builtin_amdgcn_ballot_w64(lc);
+#ifdef QH_PATH_TRACE
+            tr.enc_coop |= lm;
+#endif
             uint32_t p0 = 0;
             if (sz)
                 p0 = emit_dense(wv->in, rs, re, mode, z, wv->dense, ds,
@@ -1019,7 +1033,11 @@ struct EncPolicyT
                                               uint8_t *dst)
     {
         st = 0;
-        return enc_big_sizes(in, mode, sm, wv, cnt, to, sp, sz, dst);
+        return enc_big_sizes(in, mode, sm, wv, cnt, to, sp, sz, dst
+#ifdef QH_PATH_TRACE
+                             , tr
+#endif
+                             );
     }
     // a big tile whose output does not fit a slot (qhuff_pipeline.h), after
     // the pending tiles are flushed: base from the look-back
@@ -1071,7 +1089,11 @@ template <class SM>
 __device__ __forceinline__ bool
 enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
               QH_LDS EncWave *wv, uint32_t cnt, TileOffs to, Span sp,
-              uint32_t &sz, uint8_t *dst)
+              uint32_t &sz, uint8_t *dst
+#ifdef QH_PATH_TRACE
+              , PathTrace &tr
+#endif
+              )
 {
     using P = EncPolicyT<SM, true>;
     P pol{in, mode, sm, wv};
@@ -1125,6 +1147,9 @@ enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
                 sz = z.size;
             }
             const uint32_t n = read_lane(sz, i0);
+#ifdef QH_PATH_TRACE
+            tr.lone += 1;
+#endif
             fits = fits && run + n <= kBigSlotBytes;
             if (fits && lane == i0 && n)
             {
@@ -1168,6 +1193,9 @@ enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
         wave_sync();
         i0 = i1;
     }
+#ifdef QH_PATH_TRACE
+    tr.add(pol.tr);                          // (the units' counts)
+#endif
     return fits;
 }
 

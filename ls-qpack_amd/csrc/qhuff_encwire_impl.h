@@ -273,6 +273,9 @@ struct EncWirePolicyT
                                      // second dword until codec())
     EncSize z;                       // its literal
     uint32_t dense;                  // wave-uniform: tile from the dense stream
+#ifdef QH_PATH_TRACE
+    PathTrace tr;                    // (diagnostic) the current tile's paths
+#endif
 
     // staged tile: chunks into the LDS stage; the tile's items on their way
     __device__ __forceinline__ void stage_in(const Chunks<kChunks> &ch,
@@ -324,6 +327,10 @@ struct EncWirePolicyT
             dense = read_lane(se, cnt - 1) + 64 <= kDenseBits;
             dsb = ds | (bits << 16);
         }
+#ifdef QH_PATH_TRACE
+        tr.units += 1;
+        tr.dense += dense ? 1u : 0u;
+#endif
         if (valid)
             z = dense ? item_size_bits(m, bits, re - rs)
                       : item_size_string(m, EncLds{wv->in}, rs, re, sm->len);

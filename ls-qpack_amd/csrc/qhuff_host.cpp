@@ -431,6 +431,8 @@ qhuff_device_error(qhuff_ctx *c)
 }
 
 // Profile builds: copy the stamp buffer of the last launch (synchronous).
+// Path-trace builds (QH_PATH_TRACE): the last tile launch's records,
+// kTraceWords u64 per tile (qhuff_device.h PathTrace).
 // Returns the number of u64 words available (0 in normal builds).
 extern "C" uint64_t
 qhuff_profile_read(qhuff_ctx *c, uint64_t *dst, uint64_t max_words)
@@ -525,10 +527,43 @@ prepare_launch(qhuff_ctx *c, uint64_t tiles, hipStream_t st)
 }
 
 static Coord
-coord(qhuff_ctx *c, uint64_t tiles)
+coord(qhuff_ctx *c, uint64_t tiles, hipStream_t st)
 {
     Coord k;
     k.prof = nullptr;
+#ifdef QH_PATH_TRACE
+    {
+        // one record per tile of this launch, zeroed ahead of it on its
+        // stream (qhuff_device.h PathTrace; a failed allocation leaves no
+        // words to read)
+        const size_t words = (size_t) tiles * kTraceWords;
+        if (words > c->prof_cap)
+        {
+            if (c->prof)
+            {
+                (void) hipDeviceSynchronize();
+                (void) hipFree(c->prof);
+            }
+            c->prof = nullptr;
+            c->prof_cap = 0;
+            const size_t cap = words < 4096 * kTraceWords ? 4096 * kTraceWords
+                                                          : words;
+            if (hipMalloc((void **) &c->prof, cap * 8) == hipSuccess)
+                c->prof_cap = cap;
+            else
+                c->prof = nullptr;
+        }
+        c->prof_words = 0;
+        if (c->prof
+            && hipMemsetAsync(c->prof, 0, words * 8, st) == hipSuccess)
+        {
+            c->prof_words = words;
+            k.prof = c->prof;
+        }
+    }
+#else
+    (void) st;
+#endif
 #ifdef QHUFF_PROFILE
     {
         const size_t words = (size_t) c->n_cu * 32 * kProfIters * kProfSlots;
@@ -806,6 +841,9 @@ tile_launch(qhuff_ctx *c, uint32_t n, uint64_t tile_strings, uint64_t wpb,
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0)
     {
+#ifdef QH_PATH_TRACE
+        c->prof_words = 0;               // (no tile, no record)
+#endif
         HIPCHK(c, hipMemsetAsync(out_off, 0, 4, st));
         return QHUFF_OK;
     }
@@ -813,7 +851,7 @@ tile_launch(qhuff_ctx *c, uint32_t n, uint64_t tile_strings, uint64_t wpb,
     int rc = prepare_launch(c, tiles, st);
     if (rc)
         return rc;
-    Coord k = coord(c, tiles);
+    Coord k = coord(c, tiles, st);
     const uint32_t grid = grid_for(tiles, wpb, cap, &k.spread);
     rc = body(k, grid);
     if (rc)

@@ -707,6 +707,11 @@ tile_pipeline(P &pol, const Coord &c, const Tickets &tk, uint32_t t0,
                           out_off, status, n, lbb);
             prof_stamp(c, kProfIters - 1, 3);
         }
+#ifdef QH_PATH_TRACE
+        // (diagnostic builds) t's record: every decision has been taken
+        pol.tr.write(c, t, sp_cur.staged, fast ? 1u : bigslot ? 2u : 3u);
+        pol.tr = PathTrace();
+#endif
         wave_sync();
         prof_stamp(c, it, 6);
 

@@ -314,6 +314,9 @@ struct StreamPolicy
     StreamIo io;
     uint32_t slot0;                  // this lane's arena slot (current tile)
     StreamEnd slow_end;              // (slow_size -> slow_tile)
+#ifdef QH_PATH_TRACE
+    PathTrace tr;                    // (diagnostic) the current tile's paths
+#endif
 
     __device__ __forceinline__ void stage_in(const Chunks<kNch> &ch,
                                              const Span &sp, const Offs &)
@@ -341,6 +344,10 @@ struct StreamPolicy
             valid & (hl > kStreamFixMaxLen));
         slot0 = fixed ? kFixStride * lane
                       : 3 * lane + (uint32_t) ((8ull * (to.o0 - A)) / 5);
+#ifdef QH_PATH_TRACE
+        tr.units += 1;
+        tr.var += fixed ? 0u : 1u;
+#endif
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
         *sz = 0;

@@ -359,6 +359,9 @@ struct WirePolicy
     QH_LDS DecWave *wv;
     WireLimit lim;
     uint32_t slot0;                  // this lane's arena slot (current tile)
+#ifdef QH_PATH_TRACE
+    PathTrace tr;                    // (diagnostic) the current tile's paths
+#endif
 
     __device__ __forceinline__ void stage_in(const Chunks<kNch> &ch,
                                              const Span &sp, const Offs &)
@@ -384,6 +387,10 @@ struct WirePolicy
             valid & (hl > kFixMaxLen));
         slot0 = fixed ? kFixStride * lane
                       : 2 * lane + (uint32_t) ((8ull * (o0 - A)) / 5);
+#ifdef QH_PATH_TRACE
+        tr.units += 1;
+        tr.var += fixed ? 0u : 1u;
+#endif
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + o1) - sp.pa);
         const bool huff = wm_huff(to.meta);

@@ -654,8 +654,10 @@ class Codec:
             pass
 
     def profile_read(self):
-        """Phase stamps of the last launch (QHUFF_PROFILE build), as a
-        numpy uint64 array, or None in a normal build."""
+        """Phase stamps of the last launch (QHUFF_PROFILE build) or the path
+        records of the last tile launch, 8 words a tile (QH_PATH_TRACE
+        build, libqhuff_trace.so), as a numpy uint64 array; None in a
+        normal build."""
         import numpy as np
         n = lib().qhuff_profile_read(self._ctx, None, 0)
         if not n:

@@ -7,7 +7,7 @@
   in wire order, repeated to n strings;
 * alphabet_c: the synthetic batch with SURVEY 8(d)'s long-code alphabet C
   (token alphabet plus ~2 % of {1, 2, 6, 92, 141});
-* tile_shares: which path each 64-string tile of a batch takes in the
+* tile_paths / tile_shares: which path each 64-string tile of a batch takes in the
   kernels, by the kernels' own rules (host arithmetic over the offsets; no
   device needed): slow tiles (input span or output past the 3 KB stages,
   qhuff_pipeline.h / qhuff_decode_impl.h), decode tiles whose arena slots are
@@ -58,6 +58,7 @@ FIX_MAX_LEN = (5 * (108 - 1)) // 8
 COOP_MIN = 128
 DENSE_BITS = 32 * (STAGE // 4 + 4 - 2)
 ENC_COOP_BITS = 1024
+BIG_SLOT = 12288              # qhuff_device.h kBigSlotBytes
 
 
 def qif_strings(paths):
@@ -109,9 +110,56 @@ def _span(a, b):
     return pa, pb
 
 
-def tile_shares(data, off, hoff):
-    """Fraction of tiles on each kernel path, for encode (input data/off,
-    payload-mode output offsets hoff) and decode (input offsets hoff)."""
+def _units_copy_by_wave(off, hoff, plen, sbits, a, b):
+    """An encode tile past the stage, strings [a, b) (enc_big_sizes): its
+    staged units -- from a string on, the strings whose aligned span fits
+    the stage -- are emitted from the out stage while they fit it, come from
+    the dense stream and the tile's output so far fits a big-tile slot; is a
+    payload above kEncCoopBits among those?"""
+    run, i0 = 0, a
+    while i0 < b:
+        pa = off[i0] & ~15
+        k = i0
+        while k < b and ((off[k + 1] + 15) & ~15) - pa <= STAGE:
+            k += 1
+        k = max(k, i0 + 1)                   # (a string alone: by its lane)
+        ut = hoff[k] - hoff[i0]
+        if run + ut > BIG_SLOT:
+            return False                     # (sized only from here on)
+        if (k > i0 + 1 or ((off[k] + 15) & ~15) - pa <= STAGE) \
+                and plen[off[k]] - plen[pa] + 64 <= DENSE_BITS \
+                and ut + 64 <= STAGE \
+                and (sbits[i0:k] > ENC_COOP_BITS).any():
+            return True
+        run += ut
+        i0 = k
+    return False
+
+
+def tile_paths(data, off, hoff):
+    """One boolean per 64-string tile and path, for encode (input data/off,
+    payload-mode output offsets hoff) and decode (input offsets hoff), both
+    buffers 16-byte aligned -- what tile_shares() averages:
+
+      dec_staged / enc_staged  the tile's aligned input span fits the stage
+      dec_fast / enc_fast      ... and its output the out stage: neither a
+                               big nor a slow tile.  (The full decode kernel
+                               sends a `coop` tile through a big-tile slot
+                               all the same: it leaves the out stage iff
+                               dec_fast & ~coop; the lean one iff dec_fast.)
+      var_arena                a dec_fast tile with a string above kFixMaxLen
+      coop                     a decode tile with a string above kCoopMin
+                               that the whole wave decodes: in a staged
+                               tile, or in a staged unit of a tile past the
+                               stage (not a string that alone passes it)
+      dense                    an enc_fast tile coded from the dense stream
+      enc_coop                 an encode tile with a payload above
+                               kEncCoopBits that the whole wave copies: in a
+                               dense tile, or in a unit of a tile past the
+                               stage that is emitted from the out stage
+
+    (tests/test_path_trace.py holds them against the kernels' own record of
+    the path each tile took.)"""
     off = off.astype(np.int64)
     hoff = hoff.astype(np.int64)
     t0, t1 = _tile_bounds(off)
@@ -127,8 +175,13 @@ def tile_shares(data, off, hoff):
     var_arena = dec_fast & (max_hl > FIX_MAX_LEN)
     # a cooperative string: above COOP_MIN Huffman bytes (its bitmap lives
     # in its own arena slot, qhuff_decode_impl.h coop_decode), in a staged
-    # tile -- fast, or big and staged whole
-    coop = dec_staged & (max_hl > COOP_MIN)
+    # tile -- fast, or big and staged whole -- or in a staged unit of a tile
+    # past the stage (dec_big_sizes): every string but one whose own aligned
+    # span passes the stage, which its lane walks in global memory
+    own = ((hoff[1:] + 15) & ~15) - (hoff[:-1] & ~15)
+    wave = (hl > COOP_MIN) & (own <= STAGE)
+    coop = (np.logical_or.reduceat(wave, t0) if len(hl)
+            else np.zeros(nt, bool))
     # ---- encode tiles (payload mode) ----
     ea, eb = off[t0], off[t1]
     epa, epb = _span(ea, eb)
@@ -143,6 +196,23 @@ def tile_shares(data, off, hoff):
     big = (np.maximum.reduceat(sbits, t0) if len(sbits)
            else np.zeros(nt, np.int64))
     enc_coop = dense & (big > ENC_COOP_BITS)
+    for j in np.nonzero(~enc_staged & (big > ENC_COOP_BITS))[0]:
+        enc_coop[j] = _units_copy_by_wave(off, hoff, plen, sbits,
+                                          int(t0[j]), int(t1[j]))
+    return {"dec_staged": dec_staged, "dec_fast": dec_fast,
+            "var_arena": var_arena, "coop": coop, "enc_staged": enc_staged,
+            "enc_fast": enc_fast, "dense": dense, "enc_coop": enc_coop}
+
+
+def tile_shares(data, off, hoff):
+    """Fraction of tiles on each kernel path (tile_paths), for encode (input
+    data/off, payload-mode output offsets hoff) and decode (input offsets
+    hoff)."""
+    p = tile_paths(data, off, hoff)
+    off = off.astype(np.int64)
+    nt = len(p["dec_fast"])
+    dec_fast, var_arena, coop = p["dec_fast"], p["var_arena"], p["coop"]
+    enc_fast, dense, enc_coop = p["enc_fast"], p["dense"], p["enc_coop"]
     f = lambda m: round(float(m.mean()), 4) if nt else 0.0
     hist = np.percentile(np.diff(off), [50, 90, 99, 100]) if len(off) > 1 \
         else [0, 0, 0, 0]

@@ -10,7 +10,9 @@ say which side of every comparison a tile is on, from the constants of the
 headers written out as numbers; DECODE and ENCODE name one tile per edge
 and side.
 tests/test_limits.py checks the fixtures against the model (CPU) and the
-kernels against the oracle on them (GPU); the wire, stream and shim tests
+kernels against the oracle on them (GPU); tests/test_path_trace.py checks
+the model itself against the kernels' own record of the path each tile took
+(trace_expect / trace_expect_enc, coop_expect); the wire, stream and shim tests
 take some of the same strings through their entry points.  The resident
 service has a cutter and a tile loop of its own: svc_pieces(),
 classify_svc() / classify_svc_enc(), SVC_DECODE and SVC_ENCODE, with
@@ -24,7 +26,7 @@ import numpy as np
 
 import _paths  # noqa: F401
 import oracle_lib as O
-from test_coop_model import coop_model, seg_bits  # noqa: F401
+from test_coop_model import coop_model, coop_walks, seg_bits  # noqa: F401
 
 # ---- the headers' constants, as numbers --------------------------------------
 
@@ -199,7 +201,7 @@ def _unit(off, sizes, lo, hi, t0):
     return u
 
 
-def classify(off, base_residue, oracle_sizes):
+def classify(off, base_residue, oracle_sizes, lean=False):
     """The path of every 64-string tile of a decode batch through the full
     kernel (tile_pipeline, DecPolicyT::codec_range, dec_big_sizes): off the
     n + 1 offsets as the kernel gets them, base_residue the data pointer
@@ -225,7 +227,10 @@ def classify(off, base_residue, oracle_sizes):
 
     A unit holds at most floor(3072 / 129) = 23 strings above kCoopMin, so
     the `popcount(coop) > 48` branch of codec_range cannot be reached while
-    kDecInCap is 3072; no fixture is built for it."""
+    kDecInCap is 3072; no fixture is built for it.
+
+    lean: the lean kernel instead (DecPolicyT<..., Full = false>, kBig and
+    kCoop off): see _lean()."""
     off = [int(x) for x in off]
     sizes = [int(x) for x in oracle_sizes]
     n = len(off) - 1
@@ -270,8 +275,31 @@ def classify(off, base_residue, oracle_sizes):
             info["copy_out"] = [i for u in info["units"] if not u["lone"]
                                 for i in range(u["lo"], u["hi"])
                                 if sizes[t0 + i] > COPY_MIN]
-        tiles.append(info)
+        tiles.append(_lean(info) if lean else info)
     return tiles
+
+
+def _lean(info):
+    """A tile of the full kernels' model as the lean kernels code it
+    (tile_pipeline with P::kBig and P::kCoop false): "fast" iff the tile is
+    staged and its output <= 3008, otherwise "slow" (P::slow_tile, out of
+    line); no slots, no strings for the whole wave.  A staged tile's one
+    unit is the codec's call -- its arena, or its dense bit, as in the full
+    kernel; an unstaged tile is sized and coded in global memory, no
+    unit."""
+    t = dict(info)
+    t["units"] = []
+    if t["staged"]:
+        u = {k: v for k, v in info["units"][0].items()
+             if k not in ("S", "segs")}
+        u["coop"] = []
+        t["units"] = [u]
+    t["path"] = "fast" if t["staged"] and t["total"] <= OUT_FAST else "slow"
+    if "copy_out" in t:
+        t["copy_out"] = []
+    if "coop" in t:
+        t["coop"] = []
+    return t
 
 
 def _enc_unit(raw, off, sizes, res, mode, lo, hi, t0):
@@ -295,7 +323,7 @@ def _enc_unit(raw, off, sizes, res, mode, lo, hi, t0):
                      and bits[i] > ENC_COOP_BITS]}
 
 
-def classify_enc(data, off, base_residue, mode, oracle_sizes):
+def classify_enc(data, off, base_residue, mode, oracle_sizes, lean=False):
     """The same for an encode batch (EncPolicyT::codec_range / emit,
     enc_big_sizes): data the whole input buffer, off the n + 1 offsets into
     it.  Per tile: staged; se, the code bits of the span's bytes up to the
@@ -304,7 +332,8 @@ def classify_enc(data, off, base_residue, mode, oracle_sizes):
     a string then emits -- a literal that falls back to raw counts its code
     bits all the same; total; path as classify; coop, the lanes whose
     Huffman payload is copied by the whole wave (more than 1024 bits, in a
-    dense tile or unit that is emitted from the out stage)."""
+    dense tile or unit that is emitted from the out stage).  lean: the lean
+    kernel instead, see _lean()."""
     off = [int(x) for x in off]
     sizes = [int(x) for x in oracle_sizes]
     raw = bytes(data)
@@ -346,14 +375,91 @@ def classify_enc(data, off, base_residue, mode, oracle_sizes):
                 u = unit(i0, i0 + k, t0)
                 u["run"] = run
                 fits = fits and run + u["out"] <= BIG_SLOT
+                if not fits:
+                    u["coop"] = []           # (sized only: nothing emitted)
                 run += u["out"]
                 units.append(u)
                 i0 += k
             info["units"] = units
             info["path"] = "slot" if fits else "slow"
             info["coop"] = [i for u in units for i in u["coop"]]
-        tiles.append(info)
+        tiles.append(_lean(info) if lean else info)
     return tiles
+
+
+# ---- the model as a path-trace record ------------------------------------------
+#
+# A QH_PATH_TRACE build of the library (qhuff_device.h PathTrace) writes, per
+# tile, which side of each comparison the kernel took; these give the same
+# fields from classify() / classify_enc(), for tests/test_path_trace.py.
+
+TRACE_WORDS = 8               # kTraceWords: u64 words per tile record
+TRACE_EXIT = {1: "fast", 2: "slot", 3: "slow"}
+
+
+def trace_records(words):
+    """Codec.profile_read()'s words of a path-trace build as one dict per
+    tile (the record's layout: qhuff_device.h PathTrace)"""
+    w = np.asarray(words, dtype=np.uint64).reshape(-1, TRACE_WORDS)
+    out = []
+    for r in w:
+        r = [int(x) for x in r]
+        out.append({"written": r[0] & 1, "staged": bool(r[0] & 2),
+                    "path": TRACE_EXIT.get((r[0] >> 2) & 3),
+                    "units": r[1] & 0xffff, "lone": (r[1] >> 16) & 0xffff,
+                    "var": (r[1] >> 32) & 0xffff, "dense": r[1] >> 48,
+                    "coop": r[2], "fail": r[3],
+                    "S": r[4] & 0xffffffff if r[4] >> 63 else None,
+                    "rounds": (r[4] >> 32) & 0xffff if r[4] >> 63 else None,
+                    "enc_coop": r[5]})
+    return out
+
+
+def _mask(lanes):
+    m = 0
+    for i in lanes:
+        m |= 1 << i
+    return m
+
+
+def coop_expect(strings, info):
+    """What the cooperative decode of one decode tile does, by the model:
+    strings the tile's Huffman strings, info its classify() entry.  Per unit
+    with cooperative lanes coop_walks(h, S) for each of them -> (fail, S,
+    rounds): fail the mask of the lanes the model hands back to their own
+    lane (None), OR-ed over the units; S and rounds those of the first such
+    unit, as the record keeps them (None, None without one).  rounds is the
+    largest of the unit's strings' rounds, the rejected ones included: B is
+    one loop for the wave, over before W rejects anything."""
+    fail, S, rounds = 0, None, None
+    for u in info["units"]:
+        if not u["coop"]:
+            continue
+        rs = [coop_walks(strings[i], u["S"]) for i in u["coop"]]
+        fail |= _mask(i for i, r in zip(u["coop"], rs) if r[0] is None)
+        if S is None:
+            S, rounds = u["S"], max(r[1] for r in rs)
+    return fail, S, rounds
+
+
+def trace_expect(strings, info):
+    """The record of a decode tile by the model (full or lean entry)"""
+    units = [u for u in info["units"] if not u["lone"]]
+    fail, S, rounds = coop_expect(strings, info)
+    return {"written": 1, "staged": info["staged"], "path": info["path"],
+            "units": len(units), "lone": len(info["units"]) - len(units),
+            "var": sum(1 for u in units if u["arena"] == "var"),
+            "coop": _mask(c for u in units for c in u["coop"]),
+            "fail": fail, "S": S, "rounds": rounds}
+
+
+def trace_expect_enc(info):
+    """The record of an encode tile by the model (full or lean entry)"""
+    units = [u for u in info["units"] if not u["lone"]]
+    return {"written": 1, "staged": info["staged"], "path": info["path"],
+            "units": len(units), "lone": len(info["units"]) - len(units),
+            "dense": sum(1 for u in units if u["dense"]),
+            "enc_coop": _mask(info["coop"])}
 
 
 # ---- the fixtures ------------------------------------------------------------------

@@ -62,6 +62,15 @@ def coop_model(h, S=None):
     """(output bytes, rounds) of coop_decode for the Huffman string h (alone
     in its tile unless S is given), or None where the kernel falls back to
     the one-lane decode."""
+    out, rounds = coop_walks(h, S)
+    return None if out is None else (out, rounds)
+
+
+def coop_walks(h, S=None):
+    """coop_model with the rounds of a string that falls back as well:
+    (output bytes or None, rounds).  The kernel's B loop is one loop for the
+    whole wave and ends before any string is rejected, so a string that
+    fails afterwards has gone its rounds like any other."""
     at = _walker(h)
     b1 = nbits = 8 * len(h)
     if S is None:
@@ -124,16 +133,16 @@ def coop_model(h, S=None):
     T = [C[0]] + [K[k - 1] + (sum(1 for q in marks if X[k - 1] <= q < stop[k])
                               if met[k - 1] else 0) for k in range(1, nseg)]
     if sum(T) > (8 * len(h)) // 5:
-        return None
+        return None, rounds
     # W
     out = []
     for k in range(nseg):
         o = []
         x, m, _, bad = walk(0 if k == 0 else cs[k - 1], stop[k], "emit", o)
         if bad or m != T[k] or (k + 1 < nseg and x != cs[k]):
-            return None
+            return None, rounds
         if k + 1 == nseg and b1 - x >= 8:
-            return None                      # padding of 8 bits or more
+            return None, rounds              # padding of 8 bits or more
         out += o
     return bytes(out), rounds
 

@@ -326,6 +326,16 @@ def _long_tiles(rng, n_tiles, lens, alpha, corrupt=None):
     return pack(strs)
 
 
+def coop_long_input(alpha):
+    """test_decode_cooperative_long_strings' batch (tests/test_path_trace.py
+    sends the same through the path-trace build)"""
+    rng = random.Random(len(alpha) * 31)
+    lens = [150, 160, 161, 170, 200, 256, 300, 480, 700, 1000, 1461, 1900, 2400]
+    if alpha == "all":
+        lens = [80, 81, 100, 130, 200, 400, 700, 900]   # ~2.6x expansion
+    return _long_tiles(rng, 3 * len(lens), lens, ALPHAS[alpha])
+
+
 @pytest.mark.parametrize("alpha", ["token", "all", "long"])
 def test_decode_cooperative_long_strings(codec, alpha):
     """Strings above the cooperative threshold (128 Huffman bytes) are
@@ -333,21 +343,14 @@ def test_decode_cooperative_long_strings(codec, alpha):
     the write walk): lengths around the threshold and the segment sizes, up
     to the stage's whole span, each in a tile of short strings; bit-exact
     against the oracle."""
-    rng = random.Random(len(alpha) * 31)
-    lens = [150, 160, 161, 170, 200, 256, 300, 480, 700, 1000, 1461, 1900, 2400]
-    if alpha == "all":
-        lens = [80, 81, 100, 130, 200, 400, 700, 900]   # ~2.6x expansion
-    data, off = _long_tiles(rng, 3 * len(lens), lens, ALPHAS[alpha])
+    data, off = coop_long_input(alpha)
     out, oo, st = check_decode(codec, data, off)
     assert not st.any()
     check_decode(codec, data, off, pad_front=7)
 
 
-def test_decode_cooperative_many_per_tile(codec):
-    """Tiles holding 2-12 cooperative strings of 130-900 Huffman bytes
-    (several strings share the 64 lanes; S from their total, down to the
-    64-bit segment minimum) in random places among short ones, a few of
-    them invalid; statuses and bytes against the oracle."""
+def coop_many_input():
+    """test_decode_cooperative_many_per_tile's batch"""
     rng = random.Random(777)
     strs = []
     for t in range(48):
@@ -365,15 +368,21 @@ def test_decode_cooperative_many_per_tile(codec):
                 strs.append(O.huffman_enc(
                     bytes(rng.choice(ALPHAS["token"])
                           for _ in range(rng.randrange(0, 40)))))
-    data, off = pack(strs)
+    return pack(strs)
+
+
+def test_decode_cooperative_many_per_tile(codec):
+    """Tiles holding 2-12 cooperative strings of 130-900 Huffman bytes
+    (several strings share the 64 lanes; S from their total, down to the
+    64-bit segment minimum) in random places among short ones, a few of
+    them invalid; statuses and bytes against the oracle."""
+    data, off = coop_many_input()
     out, oo, st = check_decode(codec, data, off)
     assert (st == 0).sum() > 2900
 
 
-def test_decode_cooperative_invalid(codec):
-    """Invalid long strings (an EOS code inside, a flipped bit, non-ones or
-    over-long padding, a cut string) take the one-lane decode again: status
-    and bytes as the reference decoder."""
+def coop_invalid_input():
+    """test_decode_cooperative_invalid's batch"""
     rng = random.Random(4242)
 
     def corrupt(i, h):
@@ -392,8 +401,14 @@ def test_decode_cooperative_invalid(codec):
             h = h[:-3]                               # cut
         return h
 
-    data, off = _long_tiles(rng, 120, [200, 500, 1200], ALPHAS["token"],
-                            corrupt)
+    return _long_tiles(rng, 120, [200, 500, 1200], ALPHAS["token"], corrupt)
+
+
+def test_decode_cooperative_invalid(codec):
+    """Invalid long strings (an EOS code inside, a flipped bit, non-ones or
+    over-long padding, a cut string) take the one-lane decode again: status
+    and bytes as the reference decoder."""
+    data, off = coop_invalid_input()
     out, oo, st = check_decode(codec, data, off)
     assert st.sum() > 20 and (st == 0).sum() > 1000
 

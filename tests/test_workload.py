@@ -66,6 +66,39 @@ def test_long_and_big_tiles_are_counted():
     assert sh["encode_coop_tile_share"] == round(1 / 3, 4)
 
 
+def test_tile_paths_are_what_the_shares_average():
+    """tile_paths on the batch above: the tile each share counts, and
+    tile_shares the mean of each array"""
+    short = [b"x" * 10] * 63
+    data, off = W.pack(short + [b"ab" * 150] + short + [b"q" * 5000] + short
+                       + [b"y"])
+    h, ho = O.encode_batch(data, off, 0)
+    p = W.tile_paths(data, off, ho)
+    assert set(p) == {"dec_staged", "dec_fast", "var_arena", "coop",
+                      "enc_staged", "enc_fast", "dense", "enc_coop"}
+    assert all(v.dtype == bool and v.shape == (3,) for v in p.values())
+    assert list(p["coop"]) == [True, False, False]
+    assert list(p["dec_staged"]) == list(p["dec_fast"]) == [True, False, True]
+    assert list(p["var_arena"]) == [True, False, False]
+    assert list(p["enc_staged"]) == list(p["enc_fast"]) == [True, False, True]
+    assert list(p["dense"]) == [True, False, True]
+    assert list(p["enc_coop"]) == [True, False, False]
+    sh = W.tile_shares(data, off, ho)
+    for key, arr in (("decode_slow_tile_share", ~p["dec_fast"]),
+                     ("decode_var_arena_share", p["var_arena"]),
+                     ("decode_coop_tile_share", p["coop"]),
+                     ("encode_slow_tile_share", ~p["enc_fast"]),
+                     ("encode_fallback_share", p["enc_fast"] & ~p["dense"]),
+                     ("encode_coop_tile_share", p["enc_coop"])):
+        assert sh[key] == round(float(arr.mean()), 4), key
+    assert sh == _shares(short + [b"ab" * 150] + short + [b"q" * 5000] + short
+                         + [b"y"])
+    assert list(sh) == ["tiles", "decode_slow_tile_share",
+                        "decode_var_arena_share", "decode_coop_tile_share",
+                        "encode_slow_tile_share", "encode_fallback_share",
+                        "encode_coop_tile_share", "raw_len_p50_p90_p99_max"]
+
+
 def test_batch_needs_full():
     """qhuff_batch_needs_full (host only): the full kernel for a batch with a
     string above 128 bytes or a 64-string tile past the 3 KB stage (the
