@@ -11,7 +11,7 @@
 // One string per lane, one 64-string tile per wave (qhuff_device.h).  The
 // tile's Huffman input is staged in the wave's LDS region as big-endian
 // dwords.  Each lane holds its bit stream as two dwords A:B and a bit
-// position (decode_string_lds): a step looks the next 13 bits up in a window
+// position (decode_string): a step looks the next 13 bits up in a window
 // table (up to two symbols of <= 13 bits), writes the entry's two symbol
 // bytes to the string's arena slot and advances by the bits consumed.
 // Codes of 14..30 bits stall their lane and are decoded together outside the
@@ -46,8 +46,8 @@ qhuff_decode_kernel(DecArgs a)
     const Tickets &tk = p.tk;
     const DecTableLoads tl = p.tl;
     prof_realtime(a.c, kProfIters - 1, 11);      // (profiling) after it
-    DecPolicyT<DecSmem, Keep, Full> pol{a.in, sm,
-                                  &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)], 0};
+    DecPolicyT<DecSmem, Keep, Full> pol{
+        {a.in, sm, &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)], 0}};
 #ifdef QHUFF_PROFILE
     pol.pc = &a.c;
 #endif

@@ -1,8 +1,10 @@
-// qhuff_decode_impl.h -- the decode side of the kernels: window-table
-// step loop, arena compaction, slow tiles and the tile policy, shared by the
+// qhuff_decode_impl.h -- the decode side of the kernels: the one decoder
+// (window-table step loop and tail lookup, over the LDS stage or over global
+// memory), arena compaction, slow tiles and the tile policy, shared by the
 // batch kernel (qhuff_decode.hip) and the service kernel (qhuff_service.hip);
-// the resumable decoder (qhuff_stream_impl.h) builds on the step loop, the
-// sources, the emitters and the table staging.
+// the resumable decoder (qhuff_stream_impl.h) and the in-place one
+// (qhuff_wire_impl.h) build on the step loop, the sources, the emitters, the
+// stage policy and the table staging.
 // See qhuff_decode.hip for the algorithm.
 #pragma once
 
@@ -125,25 +127,24 @@ struct DecTableLoads
 struct DecLds                        // big-endian dwords staged in LDS
 {
     const QH_LDS uint32_t *w;
+    // (the stage has slack past the input: the walk's reads ahead are safe)
     __device__ __forceinline__ uint32_t dw(uint32_t i) const { return w[i]; }
-    // the stage has slack past the input: reading ahead is always safe
-    __device__ __forceinline__ uint32_t dw_ahead(uint32_t i, uint32_t) const
-    {
-        return w[i];
-    }
 };
-struct DecGlb                        // raw little-endian bytes in global
+// The one source in global memory: raw little-endian bytes from the 16-byte-
+// aligned base w, of which this lane's string (or chunk) ends at bit bitend
+// (8 * re, its end relative to w).  Page safety: dw(i) loads only when dword
+// i holds a byte at or before the string's last one, so no dword is touched
+// that the caller's buffer does not reach.  window_walk() reads src.dw() up
+// to two dwords past the last bit; those reads come back as the constant,
+// whose value does not matter: the main steps consume real bits only, a long
+// code that runs into it is longer than rem, and tail_lookup() pads from rem.
+struct DecGlb
 {
     const QH_GLB uint32_t *w;
+    uint32_t bitend;
     __device__ __forceinline__ uint32_t dw(uint32_t i) const
     {
-        return bswap32(w[i]);
-    }
-    // never touch a dword that holds no byte of the string (page safety)
-    __device__ __forceinline__ uint32_t dw_ahead(uint32_t i,
-                                                 uint32_t bitend) const
-    {
-        return i * 32 < bitend ? bswap32(w[i]) : 0u;
+        return i * 32 < bitend ? bswap32(w[i]) : 0xffffffffu;
     }
 };
 
@@ -173,145 +174,13 @@ long_code(uint32_t w, const QH_LDS uint16_t *s_sorted, uint32_t *len)
     return s_sorted[idx];
 }
 
-// One main-phase step: look the top 12 bits up, emit up to two symbols,
-// shift them out of the 64-bit buffer hi:lo and refill one dword when fewer
-// than 32 valid bits remain.  GATED: lanes with act == false keep their
-// state (consume 0 bits, emit 0 bytes).  Returns false for a lane that hit
-// the EOS code (the string is rejected, D3 (a)).
-template <bool GATED, class Emit>
-__device__ __forceinline__ bool
-main_step(bool act, uint32_t d, uint32_t &hi, uint32_t &lo, uint32_t &bits,
-          uint32_t &rem, uint32_t &p, const QH_LDS uint32_t *s_win,
-          const QH_LDS uint16_t *s_sorted, Emit &emit)
-{
-    uint32_t e = s_win[hi >> (32 - kWinBits)];
-    bool ok = true;
-    if (__builtin_amdgcn_ballot_w64((GATED ? act : true) & (e < (1u << 24))))
-    {
-        // a code of 13..30 bits: synthesize the entry of a one-symbol step
-        uint32_t L;
-        const uint32_t sym = long_code(hi, s_sorted, &L);
-        const bool lng = (GATED ? act : true) & (e < (1u << 24));
-        ok = !(lng & (sym == 256));
-        const uint32_t el = (sym & 0xff) | (L << 8) | (L << 12) | (1u << 24)
-                          | ((32u - L) << 26);
-        e = lng ? (ok ? el : 0u) : e;
-    }
-    if (GATED)
-        e = act ? e : 0u;
-    const uint32_t nb = (e >> 24) & 3;       // 0 for a held lane
-    const uint32_t k = e >> 26;              // 32 - bits consumed
-    const uint32_t cc = 32u - k;
-    emit(e, nb);
-    const uint32_t sh = __builtin_amdgcn_alignbit(hi, lo, k);
-    hi = GATED ? (nb ? sh : hi) : sh;
-    lo = lo << (cc & 31);                    // held: cc = 32, no shift
-    const uint32_t used = GATED ? (nb ? cc : 0u) : cc;
-    bits -= used;
-    rem -= used;
-    const bool need = bits < 32;
-    const uint32_t dd = need ? d : 0u;
-    hi |= dd >> (bits & 31);
-    lo |= dd << ((32 - bits) & 31);
-    p += need ? 1 : 0;
-    bits += need ? 32 : 0;
-    return ok;
-}
-
-// Decode one string whose bits are [bit0, bitend) of the big-endian dword
-// stream `src`; emitted bytes go through `emit`.  Returns the number of
-// output bytes, or -1 - k for a rejected string (k: the bytes emitted before
-// the error, every symbol before the EOS code or before the bad padding).
-// Three wave-uniform phases:
-//   1. while every lane has >= 32 real bits ahead: ungated steps;
-//   2. while some lane does: steps predicated on the lane's own state;
-//   3. the last < 32 bits, padded with ones, with the D3 tail rule.
-template <class Src, class Emit>
-__device__ __forceinline__ int
-decode_string(const Src &src, uint32_t bit0, uint32_t bitend,
-              const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_sorted,
-              Emit &emit)
-{
-    uint32_t rem = bitend - bit0;            // real bits not yet consumed
-    uint32_t hi = 0, lo = 0, bits = 0, p = 0;
-    if (rem)
-    {
-        const uint32_t i0 = bit0 >> 5, sk = bit0 & 31;
-        const uint32_t a = src.dw(i0), b = src.dw_ahead(i0 + 1, bitend);
-        hi = sk ? __builtin_amdgcn_alignbit(a, b, 32 - sk) : a;
-        lo = b << sk;
-        bits = 64 - sk;
-        p = i0 + 2;
-    }
-    bool bad = false;
-
-    // Invariant in phases 1-2: the buffer holds >= 32 valid bits and ends
-    // on a dword boundary (p).  A held lane's two arena byte writes land at
-    // its current end and are overwritten or ignored.
-    if (!__builtin_amdgcn_ballot_w64(rem < 32))
-    do
-    {
-        const uint32_t d = src.dw_ahead(p, bitend);
-        const bool ok = main_step<false>(true, d, hi, lo, bits, rem, p, s_win,
-                                         s_sorted, emit);
-        bad |= !ok;
-        rem = ok ? rem : 0u;                 // leave phase 1 (rare)
-    } while (!__builtin_amdgcn_ballot_w64(rem < 32));
-    bool act = rem >= 32 && !bad;
-    if (__builtin_amdgcn_ballot_w64(act))
-    do
-    {
-        const uint32_t d = src.dw_ahead(p, bitend);
-        const bool ok = main_step<true>(act, d, hi, lo, bits, rem, p, s_win,
-                                        s_sorted, emit);
-        bad |= !ok;
-        act = act & ok & (rem >= 32);
-    } while (__builtin_amdgcn_ballot_w64(act));
-
-    // epilogue: the last < 32 bits, padded with ones; D3 tail rule
-    bool fin = bad || rem == 0;
-    if (__builtin_amdgcn_ballot_w64(!fin))
-    do
-    {
-        const uint32_t w = hi | (0xffffffffu >> (rem & 31));
-        const uint32_t e = s_win[w >> (32 - kWinBits)];
-        const uint32_t ns = ent_ns(e), ct = ent_c(e), l0 = ent_l0(e);
-        const bool two = (ns == 2) & (ct <= rem);
-        uint32_t c = two ? ct : (ns ? l0 : 31u);
-        uint32_t val = e;
-        bool eos = false;
-        if (__builtin_amdgcn_ballot_w64(!fin & (ns == 0) & (rem > kWinBits)))
-        {
-            uint32_t L;
-            const uint32_t sym = long_code(w, s_sorted, &L);
-            const bool lng = (ns == 0) & (rem > kWinBits);
-            c = lng ? L : c;
-            val = lng ? sym : val;
-            eos = lng & (sym == 256);
-        }
-        // c > rem: what is left is padding -- at most 7 bits of EOS prefix
-        const bool over = c > rem;
-        const uint32_t ones = 0xffffffffu >> ((32 - rem) & 31);
-        const bool tail_bad = rem >= 8 || (w >> ((32 - rem) & 31)) != ones;
-        const bool live = !fin;
-        bad |= live & ((over & tail_bad) | (!over & eos));
-        const bool step = live & !over & !eos;
-        const uint32_t nb = step ? (two ? 2u : 1u) : 0u;
-        c = step ? c : 0;
-        emit(val, nb);
-        const uint32_t sh = __builtin_amdgcn_alignbit(hi, lo, (32 - c) & 31);
-        hi = c ? sh : hi;
-        lo = lo << (c & 31);
-        rem -= c;
-        fin = fin | over | eos | (rem == 0);
-    } while (__builtin_amdgcn_ballot_w64(!fin));
-    return bad ? -1 - (int) emit.n : (int) emit.n;
-}
-
-// Lean variant used by the staged (LDS) path (same return value), in two
+// The decoder: decode_string() below walks one string whose bits are
+// [bit0, bitend) of the big-endian dword stream `src` -- DecLds over a staged
+// tile, DecGlb over global memory for what does not fit the stage -- in two
 // parts: window_walk(), the main phase, and tail_lookup(), the last
 // < kWinBits bits; the resumable decoder (qhuff_stream_impl.h) is built from
-// the same two.  The bit stream sits in two dwords A:B with a position t: the 32-bit window is alignbit(A, B, t) --
+// the same two.  The bit stream sits in two dwords A:B with a position t: the
+// 32-bit window is alignbit(A, B, t) --
 // ((A:B) >> t), the next bit at A's bit 31 - (32 - t) -- valid for t in
 // [0, 31] (t = 0: the window is B).  Consuming c bits lowers t; when it goes
 // negative the window moves on a dword (A = B, B = the next dword, read one
@@ -322,8 +191,7 @@ decode_string(const Src &src, uint32_t bit0, uint32_t bitend,
 // reads the hold entry: it consumes and emits nothing); the EOS check and
 // the "code runs past the end" check (the leftover would be >= 8 bits: D3)
 // live in the rare long-code branch.  The last < kWinBits bits (at most two
-// symbols) take the padded epilogue with the D3 tail rule, exactly as
-// decode_string().
+// symbols) take the padded epilogue with the D3 tail rule.
 // R2: two main steps per loop trip share one refill read of the next input
 // dword (step lab at 12 waves/CU: 8,633 vs 9,795 cycles per tile; decode
 // 62.7 vs 64.0 us in-process, profiles/r03_p); false: one read per step.
@@ -485,15 +353,18 @@ tail_lookup(uint32_t W, uint32_t rem, bool live, const QH_LDS uint32_t *s_win,
     return Tail{w, c, rem - c};
 }
 
-template <class Emit, bool R2 = true>
+// Decode one string; emitted bytes go through `emit`.  Returns the number of
+// output bytes, or -1 - k for a rejected string (k: the bytes emitted before
+// the error, every symbol before the EOS code or before the bad padding).
+template <class Src, class Emit, bool R2 = true>
 __device__ __forceinline__ int
-decode_string_lds(const QH_LDS uint32_t *src, uint32_t bit0, uint32_t bitend,
-                  const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_sorted,
-                  const QH_LDS uint16_t *s_long2, Emit &emit)
+decode_string(const Src &src, uint32_t bit0, uint32_t bitend,
+              const QH_LDS uint32_t *s_win, const QH_LDS uint16_t *s_long2,
+              Emit &emit)
 {
     RejectPastEnd stop;
-    const Walked k = window_walk<R2>(DecLds{src}, bit0, bitend - bit0, s_win,
-                                     s_long2, emit, stop);
+    const Walked k = window_walk<R2>(src, bit0, bitend - bit0, s_win, s_long2,
+                                     emit, stop);
     uint32_t bad = k.bad;
     // epilogue: the r2 bits behind the last symbols are the padding, and the
     // D3 tail rule (fewer than 8 bits, all ones) applies at once
@@ -591,7 +462,7 @@ write_bytes(QH_LDS uint8_t *d, uint32_t v, uint32_t nb)
 //   W  every lane decodes its segment again from its now exact first symbol
 //      start, into the string's arena slot at that offset, with the D3 checks.
 // A string whose W finds an error (EOS code, bad padding), or whose counts
-// or exits disagree, is decoded again by its own lane (decode_string_lds),
+// or exits disagree, is decoded again by its own lane (decode_string),
 // so the result is always the one-lane result.  Cost: ~3 walks of S bits
 // per string against one walk of the whole string.
 #ifndef QH_COOP_MIN
@@ -618,7 +489,7 @@ enum WalkMode { kWalkMark, kWalkCheck, kWalkEmit };
 
 // Walk the symbols of the staged stream src that start at [pos, lim) of the
 // string ending at bitend (lim <= bitend; a walk that reaches the string's
-// last < kWinBits bits decodes them padded, as decode_string_lds), one or
+// last < kWinBits bits decodes them padded, as decode_string), one or
 // two symbols a step; pos ends on the first symbol start >= lim (or where
 // the walk stopped).  n counts the symbols.  Mark: set each symbol start's
 // bit in bm (bit x - b0).  Check: stop on a symbol start whose bit is set
@@ -1050,14 +921,21 @@ compact_wave(const QH_LDS uint8_t *src, QH_LDS uint8_t *dstb, uint32_t n)
 }
 
 
-// A tile whose input or output does not fit the stage, coded eagerly:
-// input staged -> the arena already holds the bytes (sz / st given);
-// otherwise count from global memory, then decode again to global.  The
-// tile's output base comes from base_of(total) (the batch kernel's look-back,
-// or the service's running offset); its offsets and statuses go to t_off /
-// t_status (the tile's first string).  Returns base + total.  Out of line
-// (cold), state by value.  Keep: a rejected string's output is the bytes
-// decoded before its error (DecPolicyT).
+// a staged slow tile's bytes (the decode, stream and wire kernels): the codec
+// left them in this lane's arena slot; to global byte by byte
+__device__ __forceinline__ void
+arena_to_global(const QH_LDS uint8_t *sa, uint8_t *dst, uint32_t sz)
+{
+    for (uint32_t i = 0; i < sz; ++i)
+        ((QH_GLB uint8_t *) dst)[i] = sa[i];
+}
+
+// A tile whose input or output does not fit the stage, coded eagerly
+// (the SlowTile frame, qhuff_pipeline.h): input staged -> the arena already
+// holds the bytes (sz / st given); otherwise count from global memory
+// (unless sized), then decode again to global, each string by its lane.
+// Out of line (cold), state by value.  Keep: a rejected string's output is
+// the bytes decoded before its error (DecPolicyT).
 template <bool Keep, class SM, class BaseOf>
 __device__ __noinline__ uint64_t
 dec_slow_tile(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
@@ -1065,44 +943,31 @@ dec_slow_tile(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
               uint32_t st, bool sized, uint8_t *out, uint32_t *t_off,
               uint8_t *t_status, BaseOf base_of)
 {
-    const uint32_t lane = lane_id();
-    const bool valid = lane < cnt;
+    const bool valid = lane_id() < cnt;
     const uint32_t rs = valid ? (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa) : 0;
     const uint32_t re = valid ? (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa) : 0;
-    const DecGlb src{(const QH_GLB uint32_t *) sp.pa};
+    const DecGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
     if (!sp.staged && !sized)
     {
         int r = 0;
         if (valid)
         {
             CountEmit em{0};
-            r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->sorted, em);
+            r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         sz = r >= 0 ? (uint32_t) r : Keep ? (uint32_t) (-1 - r) : 0u;
         st = r < 0 ? QHUFF_DEC_ERROR : QHUFF_DEC_OK;
     }
-    const uint32_t incl = wave_incl_scan(sz);
-    const uint32_t excl = incl - sz;
-    const uint32_t total = read_lane(incl, 63);
-    const uint64_t base = base_of(total);
-    uint8_t *dst = out + base + excl;
+    const SlowTile f = SlowTile::begin(sz, base_of);
+    uint8_t *dst = out + f.base + f.excl;
     if (sp.staged)
-    {
-        const QH_LDS uint8_t *sa = wv->arena + slot0;
-        for (uint32_t i = 0; i < sz; ++i)
-            ((QH_GLB uint8_t *) dst)[i] = sa[i];
-    }
+        arena_to_global(wv->arena + slot0, dst, sz);
     else if (valid && (Keep || st == QHUFF_DEC_OK) && sz)
     {
         GlobalEmit em{dst, 0};
-        decode_string(src, 8 * rs, 8 * re, sm->win, sm->sorted, em);
+        decode_string(src, 8 * rs, 8 * re, sm->win, sm->long2, em);
     }
-    if (valid)
-    {
-        ((QH_GLB uint32_t *) t_off)[lane] = (uint32_t) (base + excl);
-        ((QH_GLB uint8_t *) t_status)[lane] = (uint8_t) st;
-    }
-    return base + total;
+    return f.end<true>(cnt, st, t_off, t_status);
 }
 
 
@@ -1123,9 +988,9 @@ dec_tile_sizes(const uint8_t *in, QH_LDS SM *sm, uint32_t cnt, TileOffs to,
     {
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
-        const DecGlb src{(const QH_GLB uint32_t *) sp.pa};
+        const DecGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
         CountEmit em{0};
-        r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->sorted, em);
+        r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->long2, em);
     }
     SzSt o;
     o.sz = r >= 0 ? (uint32_t) r : Keep ? (uint32_t) (-1 - r) : 0u;
@@ -1143,39 +1008,28 @@ dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
 #endif
               );
 
-// the decode side of the wave pipeline (qhuff_pipeline.h, qhuff_service.hip);
-// SM: the workgroup's LDS (win, sorted).  Keep (the kernel the per-string
-// entry points use to replay where the reference stops on an invalid
-// string, qhuff_shim.cpp): a rejected string keeps, as its output, the bytes
-// decoded before the error; its status is QHUFF_DEC_ERROR all the same.
-template <class SM, bool Keep = false, bool Full = true>
-struct DecPolicyT
+// What the three policies of the decode family state once (DecPolicyT here,
+// StreamPolicy in qhuff_stream_impl.h, WirePolicy in qhuff_wire_impl.h): the
+// stage constants, the wave's LDS, the input stage that doubles as the
+// output stage, the placement of the arena slots and the compacting emit.
+template <class SM>
+struct DecStagePolicy
 {
     static constexpr bool kStatus = true;
-    // Full: the kernel for batches with big tiles (output slots) and long
-    // strings (coop_phase after the codec); the lean one codes those tiles
-    // out of line and its strings by their lanes, and its hot loop keeps its
-    // registers (qhuff_host.cpp picks the kernel per launch)
-    static constexpr bool kBig = Full;
-    static constexpr bool kCoop = Full && QH_DEC_COOP;
     static constexpr int kInCap = kDecInCap;
     static constexpr int kDepth = QH_DEPTH;       // pending tiles
     static constexpr int kOutCap = kDecStageCap;
     static constexpr int kNch = kDecNch;          // 16-byte chunks per lane
     static constexpr uint32_t kTS = kDecTS;       // strings per tile
-    using Offs = TileOffs;
     const uint8_t *in;
     QH_LDS SM *sm;
     QH_LDS DecWave *wv;
     uint32_t slot0;                  // this lane's arena slot (current tile)
-    uint64_t coop = 0;               // strings decoded by the whole wave
-#ifdef QHUFF_PROFILE
-    const Coord *pc = nullptr;       // (profiling) stamps of coop_decode
-#endif
 #ifdef QH_PATH_TRACE
     PathTrace tr;                    // (diagnostic) the current tile's paths
 #endif
 
+    template <class Offs>
     __device__ __forceinline__ void stage_in(const Chunks<kNch> &ch,
                                              const Span &sp, const Offs &)
     {
@@ -1186,6 +1040,61 @@ struct DecPolicyT
     {
         return wv->in;
     }
+    // This lane's arena slot for its bytes [o0, o1) of a unit that starts at
+    // offset A (valid: the unit's lanes): at the fixed stride when no string
+    // of the unit is longer than fix_max, else by input offset with `slack`
+    // bytes a lane (2; 3 for a chunk: qhuff_stream_impl.h).  Returns whether
+    // the slots are the fixed ones.
+    __device__ __forceinline__ bool place(uint32_t lane, uint32_t o0,
+                                          uint32_t o1, uint32_t A, bool valid,
+                                          uint32_t slack, uint32_t fix_max)
+    {
+        const bool fixed = !__builtin_amdgcn_ballot_w64(
+            valid & (o1 - o0 > fix_max));
+        slot0 = fixed ? kFixStride * lane
+                      : slack * lane + (uint32_t) ((8ull * (o0 - A)) / 5);
+#ifdef QH_PATH_TRACE
+        tr.units += 1;
+        tr.var += fixed ? 0u : 1u;
+#endif
+        return fixed;
+    }
+    // arena -> the (dead) input stage, compacted
+    __device__ __forceinline__ void emit(uint32_t excl, uint32_t sz, uint32_t)
+    {
+        QH_LDS uint8_t *stage = (QH_LDS uint8_t *) wv->in;
+        compact_wave(wv->arena + slot0, stage + excl, sz);
+    }
+};
+
+// the decode side of the wave pipeline (qhuff_pipeline.h, qhuff_service.hip);
+// SM: the workgroup's LDS (win, sorted).  Keep (the kernel the per-string
+// entry points use to replay where the reference stops on an invalid
+// string, qhuff_shim.cpp): a rejected string keeps, as its output, the bytes
+// decoded before the error; its status is QHUFF_DEC_ERROR all the same.
+template <class SM, bool Keep = false, bool Full = true>
+struct DecPolicyT : DecStagePolicy<SM>
+{
+    using Base = DecStagePolicy<SM>;
+    using Base::in;
+    using Base::sm;
+    using Base::wv;
+    using Base::slot0;
+#ifdef QH_PATH_TRACE
+    using Base::tr;
+#endif
+    // Full: the kernel for batches with big tiles (output slots) and long
+    // strings (coop_phase after the codec); the lean one codes those tiles
+    // out of line and its strings by their lanes, and its hot loop keeps its
+    // registers (qhuff_host.cpp picks the kernel per launch)
+    static constexpr bool kBig = Full;
+    static constexpr bool kCoop = Full && QH_DEC_COOP;
+    using Offs = TileOffs;
+    uint64_t coop = 0;               // strings decoded by the whole wave
+#ifdef QHUFF_PROFILE
+    const Coord *pc = nullptr;       // (profiling) stamps of coop_decode
+#endif
+
     // staged tile: decode this lane's string into its arena slot; strings
     // above kCoopMin Huffman bytes with the whole wave (coop_decode), when
     // their bitmap fits in the arena past the slots
@@ -1204,10 +1113,8 @@ struct DecPolicyT
         const bool valid = (lane >= lo) & (lane < cnt);
         const uint32_t A = read_lane(to.o0, lo);
         const uint32_t hl = to.o1 - to.o0;
-        const bool fixed = !__builtin_amdgcn_ballot_w64(
-            valid & (hl > kFixMaxLen));
-        slot0 = fixed ? kFixStride * lane
-                      : 2 * lane + (uint32_t) ((8ull * (to.o0 - A)) / 5);
+        const bool fixed = this->place(lane, to.o0, to.o1, A, valid, 2,
+                                       kFixMaxLen);
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
         // the slots end below kVarArenaBytes - slack + 1 for this span; the
@@ -1218,8 +1125,6 @@ struct DecPolicyT
         if (__builtin_popcountll(coop) > 48)
             coop = 0;
 #ifdef QH_PATH_TRACE
-        tr.units += 1;
-        tr.var += fixed ? 0u : 1u;
         tr.coop |= coop;
 #endif
         const bool mine = (coop >> lane) & 1;
@@ -1227,8 +1132,8 @@ struct DecPolicyT
         if (valid)
         {
             ArenaEmit em{wv->arena + slot0, wv->arena + slot0, 0};
-            r = decode_string_lds(wv->in, 8 * rs, mine ? 8 * rs : 8 * re,
-                                  sm->win, sm->sorted, sm->long2, em);
+            r = decode_string(DecLds{wv->in}, 8 * rs, mine ? 8 * rs : 8 * re,
+                              sm->win, sm->long2, em);
         }
         *sz = r >= 0 ? (uint32_t) r : Keep ? (uint32_t) (-1 - r) : 0u;
         *st = r < 0 ? QHUFF_DEC_ERROR : QHUFF_DEC_OK;
@@ -1284,9 +1189,9 @@ struct DecPolicyT
                                    : wv->arena + kArenaBytes - kCoopDummy
                                          + 2 * lane;
             ArenaEmit em{d0, d0, 0};
-            const int r2 = decode_string_lds(wv->in, 8 * rs,
-                                             f ? 8 * re : 8 * rs, sm->win,
-                                             sm->sorted, sm->long2, em);
+            const int r2 = decode_string(DecLds{wv->in}, 8 * rs,
+                                         f ? 8 * re : 8 * rs, sm->win,
+                                         sm->long2, em);
             r = f ? r2 : r;
         }
         if (mine)
@@ -1358,7 +1263,7 @@ struct DecPolicyT
                                               uint8_t *status, uint64_t n,
                                               const LookBack &lb)
     {
-        const uint64_t s0 = (uint64_t) t * kTS;
+        const uint64_t s0 = (uint64_t) t * Base::kTS;
         const uint64_t end = dec_slow_tile<Keep>(in, sm, wv, slot0, cnt, to,
                                                     sp, sz, st, sized, out,
                                                     out_off + s0, status + s0,
@@ -1399,7 +1304,7 @@ dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
               )
 {
     using P = DecPolicyT<SM, Keep, true>;
-    P pol{in, sm, wv, 0};
+    P pol{{in, sm, wv, 0}};
     const uint32_t lane = lane_id();
     uint32_t run = 0;                        // output bytes so far (uniform)
     bool fits = true;
@@ -1445,9 +1350,9 @@ dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
             // one string beyond the stage: its lane walks it in global memory
             const uintptr_t pa = (uintptr_t) (in + read_lane(to.o0, i0))
                                & ~(uintptr_t) 15;
-            const DecGlb src{(const QH_GLB uint32_t *) pa};
             const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - pa);
             const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - pa);
+            const DecGlb src{(const QH_GLB uint32_t *) pa, 8 * re};
             const uint32_t bound = (8 * read_lane(re - rs, i0)) / 5 + 1;
             const bool w = fits && run + bound <= kBigSlotBytes;
             int r = 0;
@@ -1456,13 +1361,13 @@ dec_big_sizes(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
                 if (w)
                 {
                     GlobalEmit em{dst + run, 0};
-                    r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->sorted,
+                    r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->long2,
                                       em);
                 }
                 else
                 {
                     CountEmit em{0};
-                    r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->sorted,
+                    r = decode_string(src, 8 * rs, 8 * re, sm->win, sm->long2,
                                       em);
                 }
                 sz = r >= 0 ? (uint32_t) r : Keep ? (uint32_t) (-1 - r) : 0u;

@@ -813,8 +813,7 @@ enc_slow_tile(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
               uint32_t cnt, TileOffs to, Span sp, uint32_t sz, bool sized,
               uint8_t *out, uint32_t *t_off, BaseOf base_of)
 {
-    const uint32_t lane = lane_id();
-    const bool valid = lane < cnt;
+    const bool valid = lane_id() < cnt;
     const EncGlb gsrc{(const QH_GLB uint32_t *) sp.pa};
     if (!sp.staged)
     {
@@ -828,16 +827,13 @@ enc_slow_tile(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
             sz = z.size;
         }
     }
-    const uint32_t incl = wave_incl_scan(sz);
-    const uint32_t excl = incl - sz;
-    const uint32_t total = read_lane(incl, 63);
-    const uint64_t base = base_of(total);
+    const SlowTile f = SlowTile::begin(sz, base_of);
     if (valid && sz)
     {
         const uint32_t adj = (uint32_t) ((uintptr_t) out & 3);
         Packer<PackGlb> pk;
         pk.sink.out = out - adj;
-        const uint32_t p0 = adj + (uint32_t) base + excl;
+        const uint32_t p0 = adj + (uint32_t) f.base + f.excl;
         pk.init(p0, p0 + sz);
         if (sp.staged)
             emit_string(EncLds{wv->in}, rs, re, mode, z.huff, z.plen, sm->enc,
@@ -845,9 +841,7 @@ enc_slow_tile(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
         else
             emit_string(gsrc, rs, re, mode, z.huff, z.plen, sm->enc, pk);
     }
-    if (valid)
-        ((QH_GLB uint32_t *) t_off)[lane] = (uint32_t) (base + excl);
-    return base + total;
+    return f.end<false>(cnt, 0, t_off, nullptr);
 }
 
 

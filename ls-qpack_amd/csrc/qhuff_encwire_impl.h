@@ -221,20 +221,16 @@ encwire_slow_tile(const uint8_t *in, QH_LDS SM *sm, QH_LDS EncWave *wv,
                   ItemOffs to, Span sp,
                   uint32_t sz, uint8_t *out, uint32_t *t_off, BaseOf base_of)
 {
-    const uint32_t lane = lane_id();
-    const bool valid = lane < cnt;
+    const bool valid = lane_id() < cnt;
     const uint32_t rs = valid ? (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa) : 0;
     const uint32_t re = valid ? (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa) : 0;
-    const uint32_t incl = wave_incl_scan(sz);
-    const uint32_t excl = incl - sz;
-    const uint32_t total = read_lane(incl, 63);
-    const uint64_t base = base_of(total);
+    const SlowTile f = SlowTile::begin(sz, base_of);
     if (valid && sz)
     {
         const uint32_t adj = (uint32_t) ((uintptr_t) out & 3);
         Packer<PackGlb> pk;
         pk.sink.out = out - adj;
-        const uint32_t p0 = adj + (uint32_t) base + excl;
+        const uint32_t p0 = adj + (uint32_t) f.base + f.excl;
         pk.init(p0, p0 + sz);
         if (sp.staged)
             emit_item(EncLds{wv->in}, rs, re, m, ival, z, sm->enc, pk);
@@ -242,9 +238,7 @@ encwire_slow_tile(const uint8_t *in, QH_LDS SM *sm, QH_LDS EncWave *wv,
             emit_item(EncGlb{(const QH_GLB uint32_t *) sp.pa}, rs, re, m,
                       ival, z, sm->enc, pk);
     }
-    if (valid)
-        ((QH_GLB uint32_t *) t_off)[lane] = (uint32_t) (base + excl);
-    return base + total;
+    return f.end<false>(cnt, 0, t_off, nullptr);
 }
 
 // the item side of the wave pipeline (qhuff_pipeline.h): a lean policy over

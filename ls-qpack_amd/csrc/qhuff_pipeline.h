@@ -95,25 +95,11 @@ all_lanes(T v)
     return v;
 }
 
-// Output base of a slow tile (P::slow_tile / slow_tile_at): the batch
-// kernel's look-back, or a base the caller already has (the service kernel
-// codes a request's tiles in order in one wave).
-struct LookBackBase
-{
-    Coord c;
-    uint32_t t;
-    __device__ __forceinline__ uint64_t operator()(uint32_t total) const
-    {
-        LookBack lb;
-        lb.start(c, t, total);
-        lb.super_agg(c);
-        lb.poll(c);
-        return lb.finish(c);
-    }
-};
-// ... or a look-back already started (its aggregate published, its super
-// add returned: the batch kernel's slow tiles, published before the wave's
-// pending tiles are flushed)
+// Output base of a slow tile (P::slow_tile / slow_tile_at): a look-back
+// already started (its aggregate published, its super add returned: the
+// batch kernel's slow tiles, published before the wave's pending tiles are
+// flushed), or a base the caller already has (the service kernel codes a
+// request's tiles in order in one wave).
 struct StartedBase
 {
     Coord c;
@@ -130,6 +116,46 @@ struct FixedBase
     __device__ __forceinline__ uint64_t operator()(uint32_t) const
     {
         return base;
+    }
+};
+
+// The frame of every *_slow_tile function (a tile coded out of line, each
+// string by its lane).  begin(): the sizes sz scanned and the tile's output
+// base from base_of(total) -- excl: this lane's offset in the tile; between
+// the two the function writes the tile's bytes at base + excl; end(): the
+// offsets, with Status the statuses too, stored at t_off / t_status (the
+// tile's first string); returns base + total.  (Two halves around plain
+// code, not one function around a body: a body passed in changes how the
+// cold function takes its arguments, and with that the registers of the
+// kernels that call it.)
+struct SlowTile
+{
+    uint64_t base;
+    uint32_t excl, total;
+    template <class BaseOf>
+    static __device__ __forceinline__ SlowTile begin(uint32_t sz,
+                                                     BaseOf &base_of)
+    {
+        const uint32_t incl = wave_incl_scan(sz);
+        SlowTile f;
+        f.excl = incl - sz;
+        f.total = read_lane(incl, 63);
+        f.base = base_of(f.total);
+        return f;
+    }
+    template <bool Status>
+    __device__ __forceinline__ uint64_t end(uint32_t cnt, uint32_t st,
+                                            uint32_t *t_off,
+                                            uint8_t *t_status) const
+    {
+        const uint32_t lane = lane_id();
+        if (lane < cnt)
+        {
+            ((QH_GLB uint32_t *) t_off)[lane] = (uint32_t) (base + excl);
+            if constexpr (Status)
+                ((QH_GLB uint8_t *) t_status)[lane] = (uint8_t) st;
+        }
+        return base + total;
     }
 };
 

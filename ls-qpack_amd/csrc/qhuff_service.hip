@@ -250,7 +250,7 @@ qhuff_service_kernel(SvcArgs a)
             }
             else
             {
-                DecPolicyT<SvcSmem> pol{in, sm, &wv->d, 0};
+                DecPolicyT<SvcSmem> pol{{in, sm, &wv->d, 0}};
                 total = serve_tiles(pol, in, in_off, nn, nb, out, out_off,
                                     io + kSvcStatusAt);
             }

@@ -41,9 +41,9 @@ qhuff_stream_kernel(StreamArgs s)
     const Tickets &tk = p.tk;
     const DecTableLoads tl = p.tl;
     const uint32_t nd = p.own;
-    StreamPolicy pol{a.in, sm,
-                     &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)],
-                     StreamIo{s.state, s.flags}, 0, StreamEnd{0, 0, 0}};
+    StreamPolicy pol{{a.in, sm,
+                      &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)], 0},
+                     StreamIo{s.state, s.flags}, StreamEnd{0, 0, 0}};
     uint32_t t0, k1, k2;
     wave_tickets(a.c, tk, &sm->tk, &t0, &k1, &k2);
     auto tables = [&, tl]() {

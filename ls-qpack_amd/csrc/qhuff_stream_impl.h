@@ -2,7 +2,8 @@
 // the tree node the string's earlier chunks ended on to the node this one
 // ends on (qhuff_decode_stream, include/qhuff.h).  See qhuff_stream.hip.
 // Here: the nodes, the pending-code start, the stop policy and the tile
-// policy; the step loop and the tail lookup are qhuff_decode_impl.h's.
+// policy; the step loop, the tail lookup, both sources (the stage, and
+// DecGlb for chunks past it) and the stage policy are qhuff_decode_impl.h's.
 #pragma once
 
 #include "qhuff_decode_impl.h"
@@ -46,19 +47,6 @@ node_find(const QH_LDS uint32_t *s_nodes, uint32_t key)
     return lo;
 }
 
-// The chunk's source past the stage: raw little-endian bytes in global
-// (staged chunks read DecLds)
-struct StreamGlb
-{
-    const QH_GLB uint32_t *w;
-    uint32_t bitend;
-    // never touch a dword that holds no byte of the tile (page safety)
-    __device__ __forceinline__ uint32_t dw(uint32_t i) const
-    {
-        return i * 32 < bitend ? bswap32(w[i]) : 0xffffffffu;
-    }
-};
-
 // Stop policy of window_walk(): a long code running past the chunk's end
 // stops its lane there.  The chunk's bits complete no code (the table would
 // have found it, whatever lies behind them): the rem <= 29 left are the
@@ -94,7 +82,7 @@ struct StreamEnd
 //   walk   window_walk(), the batch decoder's step loop
 //          (qhuff_decode_impl.h), under the StopAtNode policy: a long code
 //          running past the chunk's end stops the lane there (in
-//          decode_string_lds it rejects the string); the EOS code rejects
+//          decode_string it rejects the string); the EOS code rejects
 //          as before;
 //   end    the bits behind the last complete symbol (<= 29: no code is
 //          complete) are the node reached; a final chunk is accepted iff
@@ -223,19 +211,11 @@ stream_slow_tile(const uint8_t *in, QH_LDS StreamSmem *sm, QH_LDS DecWave *wv,
                  uint8_t *out, uint32_t *t_off, uint8_t *t_status,
                  BaseOf base_of)
 {
-    const uint32_t lane = lane_id();
-    const bool valid = lane < cnt;
-    const uint32_t incl = wave_incl_scan(sz);
-    const uint32_t excl = incl - sz;
-    const uint32_t total = read_lane(incl, 63);
-    const uint64_t base = base_of(total);
-    uint8_t *dst = out + base + excl;
+    const bool valid = lane_id() < cnt;
+    const SlowTile f = SlowTile::begin(sz, base_of);
+    uint8_t *dst = out + f.base + f.excl;
     if (sp.staged)
-    {
-        const QH_LDS uint8_t *sa = wv->arena + slot0;
-        for (uint32_t i = 0; i < sz; ++i)
-            ((QH_GLB uint8_t *) dst)[i] = sa[i];
-    }
+        arena_to_global(wv->arena + slot0, dst, sz);
     else
     {
         uint32_t node;
@@ -245,7 +225,7 @@ stream_slow_tile(const uint8_t *in, QH_LDS StreamSmem *sm, QH_LDS DecWave *wv,
         {
             const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
             const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
-            const StreamGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
+            const DecGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
             GlobalEmit em{dst, 0};
             stream_decode(src, 8 * rs, 8 * re, node, fin, sm->win, sm->sorted,
                           sm->long2, sm->nodes, em);
@@ -253,12 +233,7 @@ stream_slow_tile(const uint8_t *in, QH_LDS StreamSmem *sm, QH_LDS DecWave *wv,
         if (valid)
             io.store(to.s0, end);
     }
-    if (valid)
-    {
-        ((QH_GLB uint32_t *) t_off)[lane] = (uint32_t) (base + excl);
-        ((QH_GLB uint8_t *) t_status)[lane] = (uint8_t) st;
-    }
-    return base + total;
+    return f.end<true>(cnt, st, t_off, t_status);
 }
 
 // the sizes, statuses and end nodes of a tile past the stage, counted in
@@ -284,7 +259,7 @@ stream_tile_sizes(const uint8_t *in, QH_LDS StreamSmem *sm, StreamIo io,
     {
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
-        const StreamGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
+        const DecGlb src{(const QH_GLB uint32_t *) sp.pa, 8 * re};
         CountEmit em{0};
         o.end = stream_decode(src, 8 * rs, 8 * re, node, fin, sm->win,
                               sm->sorted, sm->long2, sm->nodes, em);
@@ -296,38 +271,15 @@ stream_tile_sizes(const uint8_t *in, QH_LDS StreamSmem *sm, StreamIo io,
 
 // the stream side of the wave pipeline (qhuff_pipeline.h): a lean policy --
 // tiles past the stages out of line, every chunk by its lane
-struct StreamPolicy
+struct StreamPolicy : DecStagePolicy<StreamSmem>
 {
-    static constexpr bool kStatus = true;
     static constexpr bool kBig = false;
     static constexpr bool kCoop = false;
-    static constexpr int kInCap = kDecInCap;
-    static constexpr int kDepth = QH_DEPTH;
-    static constexpr int kOutCap = kDecStageCap;
-    static constexpr int kNch = kDecNch;
-    static constexpr uint32_t kTS = kDecTS;
     static constexpr uint64_t coop = 0;
     using Offs = StreamOffs;
-    const uint8_t *in;
-    QH_LDS StreamSmem *sm;
-    QH_LDS DecWave *wv;
     StreamIo io;
-    uint32_t slot0;                  // this lane's arena slot (current tile)
     StreamEnd slow_end;              // (slow_size -> slow_tile)
-#ifdef QH_PATH_TRACE
-    PathTrace tr;                    // (diagnostic) the current tile's paths
-#endif
 
-    __device__ __forceinline__ void stage_in(const Chunks<kNch> &ch,
-                                             const Span &sp, const Offs &)
-    {
-        ch.store<true>((QH_LDS u32x4 *) wv->in, sp.n16);
-    }
-    __device__ __forceinline__ void prepare(const Span &) {}
-    __device__ __forceinline__ const QH_LDS uint32_t *out_stage() const
-    {
-        return wv->in;
-    }
     // staged tile: this lane's chunk into its arena slot, its state replaced
     __device__ __forceinline__ void codec(const Offs &to, uint32_t cnt,
                                           const Span &sp, uint32_t *sz,
@@ -338,16 +290,8 @@ struct StreamPolicy
         uint32_t node;
         bool fin;
         io.load(to.s0, cnt, &node, &fin);
-        const uint32_t A = read_lane(to.o0, 0);
-        const uint32_t hl = to.o1 - to.o0;
-        const bool fixed = !__builtin_amdgcn_ballot_w64(
-            valid & (hl > kStreamFixMaxLen));
-        slot0 = fixed ? kFixStride * lane
-                      : 3 * lane + (uint32_t) ((8ull * (to.o0 - A)) / 5);
-#ifdef QH_PATH_TRACE
-        tr.units += 1;
-        tr.var += fixed ? 0u : 1u;
-#endif
+        place(lane, to.o0, to.o1, read_lane(to.o0, 0), valid, 3,
+              kStreamFixMaxLen);
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
         *sz = 0;
@@ -362,12 +306,6 @@ struct StreamPolicy
             *sz = e.status == QHUFF_DEC_ERROR ? 0u : em.n;
             io.store(to.s0, e);
         }
-    }
-    // arena -> the (dead) input stage, compacted
-    __device__ __forceinline__ void emit(uint32_t excl, uint32_t sz, uint32_t)
-    {
-        QH_LDS uint8_t *stage = (QH_LDS uint8_t *) wv->in;
-        compact_wave(wv->arena + slot0, stage + excl, sz);
     }
     __device__ __forceinline__ void slow_size(uint32_t cnt, Offs to, Span sp,
                                               uint32_t &sz, uint32_t &st)

@@ -12,7 +12,7 @@
 // of literals that lie in wire order in one buffer, a few instruction bytes
 // between them, so the tile's input is one contiguous span of that buffer
 // and is staged as the batch kernel stages a tile of packed strings.  A
-// Huffman lane takes the batch kernel's walk (decode_string_lds), a raw lane
+// Huffman lane takes the batch kernel's walk (decode_string), a raw lane
 // copies its bytes from the stage; arena, compaction, look-back and stores
 // are the batch kernel's.  The length limit of field sections is one
 // compare a lane, except for a VALUE literal within its name's upper bound
@@ -39,9 +39,9 @@ qhuff_wire_kernel(WireArgs w)
     const auto p = dec_prologue<QH_DEC_PER>(a, sm, tid);
     const Tickets &tk = p.tk;
     const DecTableLoads tl = p.tl;
-    WirePolicy pol{a.in, sm, &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)],
-                   WireLimit{(const ::qhuff_literal *) a.in_off, w.max_len},
-                   0};
+    WirePolicy pol{{a.in, sm,
+                    &sm->w[__builtin_amdgcn_readfirstlane(tid >> 6)], 0},
+                   WireLimit{(const ::qhuff_literal *) a.in_off, w.max_len}};
     uint32_t t0, k1, k2;
     wave_tickets(a.c, tk, &sm->tk, &t0, &k1, &k2);
     auto tables = [&, tl]() {

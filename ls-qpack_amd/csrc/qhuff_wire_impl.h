@@ -1,7 +1,7 @@
 // qhuff_wire_impl.h -- literals decoded where they lie in QPACK wire data
 // (qhuff_decode_wire, include/qhuff.h).  See qhuff_wire.hip.  Here: the
 // descriptor loads, the raw copy, the length limit and the tile policy; the
-// step loop, the sources, the emitters and the arena are
+// decoder, the sources, the emitters, the arena and the stage policy are
 // qhuff_decode_impl.h's.
 #pragma once
 
@@ -66,9 +66,9 @@ struct WireOffs
     }
 };
 
-// One literal walked in global memory by its lane (the batch kernel's
-// decode_string over DecGlb: only dwords that hold a byte of it are read);
-// a raw literal is its length.  Returns as decode_string.
+// One Huffman literal walked in global memory by its lane (decode_string
+// over DecGlb: no dword past its last byte is read).  Returns as
+// decode_string.
 template <class SM, class Emit>
 __device__ __forceinline__ int
 wire_walk_glb(const uint8_t *in, QH_LDS SM *sm, uint32_t pos, uint32_t len,
@@ -77,8 +77,8 @@ wire_walk_glb(const uint8_t *in, QH_LDS SM *sm, uint32_t pos, uint32_t len,
     const uintptr_t a = (uintptr_t) (in + pos);
     const uintptr_t pa = a & ~(uintptr_t) 15;
     const uint32_t rs = (uint32_t) (a - pa);
-    const DecGlb src{(const QH_GLB uint32_t *) pa};
-    return decode_string(src, 8 * rs, 8 * (rs + len), sm->win, sm->sorted, em);
+    const DecGlb src{(const QH_GLB uint32_t *) pa, 8 * (rs + len)};
+    return decode_string(src, 8 * rs, 8 * (rs + len), sm->win, sm->long2, em);
 }
 
 // the static table's name lengths (qhuff_names.h) in the code object's
@@ -282,21 +282,13 @@ wire_slow_tile(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
                BaseOf base_of)
 {
     const uint32_t lane = lane_id();
-    const bool valid = lane < cnt;
-    const uint32_t incl = wave_incl_scan(sz);
-    const uint32_t excl = incl - sz;
-    const uint32_t total = read_lane(incl, 63);
-    const uint64_t base = base_of(total);
-    uint8_t *dst = out + base + excl;
+    const SlowTile f = SlowTile::begin(sz, base_of);
+    uint8_t *dst = out + f.base + f.excl;
     if (sp.staged)
-    {
-        const QH_LDS uint8_t *sa = wv->arena + slot0;
-        for (uint32_t i = 0; i < sz; ++i)
-            ((QH_GLB uint8_t *) dst)[i] = sa[i];
-    }
+        arena_to_global(wv->arena + slot0, dst, sz);
     else
     {
-        const bool live = valid && st == QHUFF_DEC_OK && sz;
+        const bool live = lane < cnt && st == QHUFF_DEC_OK && sz;
         const bool huff = wm_huff(to.meta);
         const bool wide = live & !huff & (sz > 64);
         if (live && huff)
@@ -316,18 +308,13 @@ wire_slow_tile(const uint8_t *in, QH_LDS SM *sm, QH_LDS DecWave *wv,
             const QH_GLB uint8_t *s =
                 (const QH_GLB uint8_t *) (in + read_lane(to.pos, j));
             QH_GLB uint8_t *d =
-                (QH_GLB uint8_t *) (out + base + read_lane(excl, j));
+                (QH_GLB uint8_t *) (out + f.base + read_lane(f.excl, j));
             const uint32_t nj = read_lane(sz, j);
             for (uint32_t i = lane; i < nj; i += 64)
                 d[i] = s[i];
         }
     }
-    if (valid)
-    {
-        ((QH_GLB uint32_t *) t_off)[lane] = (uint32_t) (base + excl);
-        ((QH_GLB uint8_t *) t_status)[lane] = (uint8_t) st;
-    }
-    return base + total;
+    return f.end<true>(cnt, st, t_off, t_status);
 }
 
 // Arena slots: DecPolicyT's (qhuff_decode_impl.h), unchanged.  A slot is
@@ -342,37 +329,14 @@ static_assert(kFixMaxLen <= 8 * kFixMaxLen / 5, "a raw literal fits its slot");
 
 // the in-place side of the wave pipeline (qhuff_pipeline.h): a lean policy
 // -- tiles past the stages out of line, every literal by its lane
-struct WirePolicy
+struct WirePolicy : DecStagePolicy<DecSmem>
 {
-    static constexpr bool kStatus = true;
     static constexpr bool kBig = false;
     static constexpr bool kCoop = false;
-    static constexpr int kInCap = kDecInCap;
-    static constexpr int kDepth = QH_DEPTH;
-    static constexpr int kOutCap = kDecStageCap;
-    static constexpr int kNch = kDecNch;
-    static constexpr uint32_t kTS = kDecTS;
     static constexpr uint64_t coop = 0;
     using Offs = WireOffs;
-    const uint8_t *in;
-    QH_LDS DecSmem *sm;
-    QH_LDS DecWave *wv;
     WireLimit lim;
-    uint32_t slot0;                  // this lane's arena slot (current tile)
-#ifdef QH_PATH_TRACE
-    PathTrace tr;                    // (diagnostic) the current tile's paths
-#endif
 
-    __device__ __forceinline__ void stage_in(const Chunks<kNch> &ch,
-                                             const Span &sp, const Offs &)
-    {
-        ch.store<true>((QH_LDS u32x4 *) wv->in, sp.n16);
-    }
-    __device__ __forceinline__ void prepare(const Span &) {}
-    __device__ __forceinline__ const QH_LDS uint32_t *out_stage() const
-    {
-        return wv->in;
-    }
     // staged tile: this lane's literal into its arena slot
     __device__ __forceinline__ void codec(const Offs &to, uint32_t cnt,
                                           const Span &sp, uint32_t *sz,
@@ -381,16 +345,8 @@ struct WirePolicy
         const uint32_t lane = lane_id();
         const bool valid = lane < cnt;
         const uint32_t o0 = to.o0(valid), o1 = to.o1();
-        const uint32_t A = to.first();
         const uint32_t hl = o1 - o0;
-        const bool fixed = !__builtin_amdgcn_ballot_w64(
-            valid & (hl > kFixMaxLen));
-        slot0 = fixed ? kFixStride * lane
-                      : 2 * lane + (uint32_t) ((8ull * (o0 - A)) / 5);
-#ifdef QH_PATH_TRACE
-        tr.units += 1;
-        tr.var += fixed ? 0u : 1u;
-#endif
+        place(lane, o0, o1, to.first(), valid, 2, kFixMaxLen);
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + o1) - sp.pa);
         const bool huff = wm_huff(to.meta);
@@ -399,8 +355,8 @@ struct WirePolicy
         {
             // (a raw lane walks no bits)
             ArenaEmit em{wv->arena + slot0, wv->arena + slot0, 0};
-            r = decode_string_lds(wv->in, 8 * rs, huff ? 8 * re : 8 * rs,
-                                  sm->win, sm->sorted, sm->long2, em);
+            r = decode_string(DecLds{wv->in}, 8 * rs, huff ? 8 * re : 8 * rs,
+                              sm->win, sm->long2, em);
         }
         const bool raw = valid & !huff;
         if (__builtin_amdgcn_ballot_w64(raw))
@@ -409,12 +365,6 @@ struct WirePolicy
         *st = r < 0 ? QHUFF_DEC_ERROR : QHUFF_DEC_OK;
         if (lim.max_len)
             wire_limit(in, sm, lim, to, cnt, *sz, *st);
-    }
-    // arena -> the (dead) input stage, compacted
-    __device__ __forceinline__ void emit(uint32_t excl, uint32_t sz, uint32_t)
-    {
-        QH_LDS uint8_t *stage = (QH_LDS uint8_t *) wv->in;
-        compact_wave(wv->arena + slot0, stage + excl, sz);
     }
     __device__ __forceinline__ void slow_size(uint32_t cnt, Offs to, Span,
                                               uint32_t &sz, uint32_t &st)

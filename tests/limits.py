@@ -211,8 +211,10 @@ def classify(off, base_residue, oracle_sizes, lean=False):
       staged   the 16-byte-aligned span of its input is <= 3072
       units    one entry for a staged tile; for an unstaged one the greedy
                runs of lanes whose aligned span is <= 3072, and a string
-               past that alone ("lone": walked in global memory, with its
-               bound 8 * len / 5 + 1 and the output before it, "run"); each
+               past that alone ("lone": walked in global memory by the
+               staged strings' decode_string over the guarded source
+               DecGlb, with its bound 8 * len / 5 + 1 and the output
+               before it, "run"); each
                with its arena ("fixed": every string <= 66 bytes, "var"),
                its cooperative lanes (> 128 bytes), their segment size S and
                segments, its output bytes and the end of its last slot
@@ -285,7 +287,8 @@ def _lean(info):
     staged and its output <= 3008, otherwise "slow" (P::slow_tile, out of
     line); no slots, no strings for the whole wave.  A staged tile's one
     unit is the codec's call -- its arena, or its dense bit, as in the full
-    kernel; an unstaged tile is sized and coded in global memory, no
+    kernel; an unstaged tile is sized and coded in global memory (decode:
+    the same decode_string over DecGlb, tests/test_global_walk.py), no
     unit."""
     t = dict(info)
     t["units"] = []

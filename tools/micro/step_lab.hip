@@ -1,4 +1,4 @@
-// Decode step-loop lab: decode_string_lds (the real kernel's codec, included
+// Decode step-loop lab: decode_string (the real kernel's codec, included
 // below) run R times on a tile staged once in each wave's LDS region, with
 // different output sinks, at 1 / 4 / 8 / 12 waves per CU.  Separates the
 // cost of the step's byte stores from its lookup / refill chain.  Prints
@@ -183,30 +183,30 @@ lab(DecArgs a, int reps, MbOut *res)
         if (MODE == 0)
         {
             ArenaEmit em{wv->arena + slot0, wv->arena + slot0, 0};
-            n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+            n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         else if (MODE == 1)
         {
             NullEmit em{0, 0};
-            n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+            n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         else if (MODE == 2)
         {
             // lane-major records: lane l's at arena + 76 * l (76 B = 19
             // dwords, odd: the 32 lanes of a group on distinct banks)
             RecEmit em{(QH_LDS uint16_t *) (wv->arena + 76 * lane), 0};
-            n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+            n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         else if (MODE == 3)
         {
             OneByteEmit em{wv->arena + slot0, wv->arena + slot0, 0};
-            n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+            n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         else if (MODE == 7 || MODE == 8)
         {
             const uint32_t sl = MODE == 7 ? slot0 : 84 * lane;
             U16Emit em{wv->arena + sl, wv->arena + sl, 0};
-            n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+            n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         else if (MODE == 9 || MODE == 10)
         {
@@ -214,8 +214,8 @@ lab(DecArgs a, int reps, MbOut *res)
             // (9) or per two steps (10, QH_REFILL2)
             ArenaEmit em{wv->arena + 108 * lane, wv->arena + 108 * lane, 0};
             n = MODE == 9
-                ? decode_string_lds<ArenaEmit, false>(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em)
-                : decode_string_lds<ArenaEmit, true>(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+                ? decode_string<DecLds, ArenaEmit, false>(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em)
+                : decode_string<DecLds, ArenaEmit, true>(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         else if (MODE == 12 || MODE == 13 || MODE == 14 || MODE == 15)
         {
@@ -228,19 +228,19 @@ lab(DecArgs a, int reps, MbOut *res)
             if (MODE == 12 || MODE == 14)
             {
                 PackEmit em{q, q, 0, 0, 0};
-                n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+                n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
             }
             else
             {
                 PackEmitM em{q, q, 0, 0, 0};
-                n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+                n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
             }
         }
         else if (MODE == 16)
         {
             // the kernel's sink in the kernel's variable slots
             ArenaEmit em{wv->arena + slot0, wv->arena + slot0, 0};
-            n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+            n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         else
         {
@@ -249,7 +249,7 @@ lab(DecArgs a, int reps, MbOut *res)
             // lanes at equal progress on distinct banks)
             constexpr uint32_t STRIDE = MODE == 4 ? 84 : MODE == 5 ? 76 : 68;
             ArenaEmit em{wv->arena + STRIDE * lane, wv->arena + STRIDE * lane, 0};
-            n = decode_string_lds(wv->in, 8 * rs, 8 * re, sm->win, sm->sorted, sm->long2, em);
+            n = decode_string(DecLds{wv->in}, 8 * rs, 8 * re, sm->win, sm->long2, em);
         }
         sum += read_lane((uint32_t) n, 63);
         const uint64_t t1 = __builtin_amdgcn_s_memtime();
@@ -311,8 +311,8 @@ lab_addtid(DecArgs a, int reps, MbOut *res)
     {
         const uint64_t t0 = __builtin_amdgcn_s_memtime();
         AddtidEmit em{(uint32_t) __builtin_amdgcn_readfirstlane((int) base), 0, 0};
-        int n = decode_string_lds(sm->in[w], 8 * rs, 8 * re, sm->win,
-                                  sm->sorted, sm->long2, em);
+        int n = decode_string(DecLds{sm->in[w]}, 8 * rs, 8 * re, sm->win,
+                              sm->long2, em);
         sum += read_lane((uint32_t) n, 63);
         const uint64_t t1 = __builtin_amdgcn_s_memtime();
         c0 += t1 - t0;
