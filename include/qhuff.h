@@ -532,6 +532,105 @@ int qhuff_decode_wire_host(qhuff_ctx *ctx, const uint8_t *buf,
                            uint32_t max_len, uint8_t *out, uint32_t *out_off,
                            uint8_t *status);
 
+/* ---- field sections and encoder streams scanned on the device -------------
+ * qhuff_scan_field_section and qhuff_scan_encoder_stream walk one chunk a
+ * call on the host, and their descriptors go up beside the wire bytes (16
+ * bytes a literal).  qhuff_scan_sections walks m chunks of one wire buffer
+ * where it lies in device memory and leaves the descriptors there, in the
+ * form and order qhuff_decode_wire reads.  QHUFF_FEATURE_SCAN_DEVICE and the
+ * symbols announce it (the ABI version is unchanged).
+ *
+ * Input: buf, the wire bytes; sec_off[0 .. m], non-decreasing: chunk i is
+ * buf[sec_off[i] .. sec_off[i + 1]); mode --
+ *   QHUFF_SCAN_FIELD_SECTION   each chunk one complete field section, by the
+ *                              rules (and their order) of
+ *                              qhuff_scan_field_section;
+ *   QHUFF_SCAN_ENCODER_STREAM  each chunk encoder-stream bytes of one
+ *                              connection, by those of
+ *                              qhuff_scan_encoder_stream: a partial last
+ *                              instruction is left unconsumed, no length
+ *                              limit.
+ * Output:
+ *   rc[m]          QHUFF_OK, QHUFF_ETRUNC or QHUFF_EPROTO: what the host
+ *                  scanner returns for that chunk alone;
+ *   consumed[m]    (may be NULL in field-section mode) encoder stream: the
+ *                  bytes of the complete instructions, 0 with QHUFF_EPROTO;
+ *                  field section: the chunk's length when OK, else 0;
+ *   lit_off[m + 1] lit_off[0] = 0; chunk i's descriptors are lits[lit_off[i]
+ *                  .. lit_off[i + 1]); a chunk that is not OK has none;
+ *                  lit_off[m] is the full count whatever max_lits is (as the
+ *                  host scanners' *n_lits under QHUFF_ERANGE);
+ *   lits           the descriptors, packed, in wire order; only those with an
+ *                  index below max_lits are written.  pos and instr are
+ *                  offsets into buf (the host scanners' pos_base =
+ *                  sec_off[i]); all 16 bytes are what the host scanner
+ *                  writes.  They satisfy qhuff_decode_wire's order rule.
+ *
+ * The buffer contract above applies.  Reads: sec_off[0 .. m] and the
+ * 16-byte-aligned blocks that contain buf[sec_off[0] .. sec_off[m]); bytes
+ * outside a chunk, the next chunk's and the read slack among them, never
+ * affect that chunk's result.  Writes: the outputs named above and nothing
+ * else; for m = 0 only lit_off[0].  Three launches on `stream` (count, sum,
+ * write), none of which waits for another workgroup; timed as
+ * QHUFF_KIND_SCAN, one entry a launch.  Scratch, 4 bytes a chunk and 4 a
+ * group of 256 chunks, belongs to the context: allocated at the first scan
+ * call, grown on demand.  One chunk is walked by one lane: a very long chunk
+ * is walked no faster than a short one.
+ *
+ * qhuff_scan_sections: device pointers, asynchronous on `stream`;
+ * QHUFF_EINVAL for a null pointer (consumed too in encoder-stream mode) or a
+ * bad mode.  The caller reads lit_off[m] and compares it with max_lits.
+ * qhuff_scan_sections_host: host pointers, synchronous, one staged round
+ * trip; QHUFF_EINVAL also for decreasing offsets; QHUFF_ERANGE when lit_off[m]
+ * > max_lits -- lit_off, rc and consumed are valid and the first max_lits
+ * descriptors are returned.
+ * qhuff_decode_sections_host: the whole decode path -- the wire bytes and
+ * offsets go up once, the scan runs, the small results come back (n =
+ * lit_off[m]), qhuff_decode_wire(max_len) runs on the descriptors where they
+ * are, and descriptors, offsets, statuses and exactly out_off[n] bytes come
+ * back.  `out` holds qhuff_decode_bound(wire bytes, 0), out_off n + 1 and
+ * status n entries (max_lits + 1 and max_lits are enough).  The results are
+ * those of the host scanner per chunk followed by qhuff_decode_wire_host on
+ * the concatenated descriptors.  QHUFF_ERANGE when n > max_lits: nothing is
+ * decoded and out, out_off and status are not written; lit_off, rc and
+ * consumed are valid and the first max_lits descriptors are returned, as
+ * by qhuff_scan_sections_host.  The context's staging buffers (pinned host
+ * and device) grow to the call's size, about the wire bytes + 21 bytes per
+ * descriptor of max_lits + the bound of `out`, and stay with the context:
+ * pass a max_lits near the count, not a loose bound.
+ * qhuff_scan_sections_cpu: the same walker source as the kernels', run on
+ * the host over host pointers: no context and no device call.  A diagnostic
+ * (as qhuff_host_chunks); returns as qhuff_scan_sections_host. */
+#define QHUFF_FEATURE_SCAN_DEVICE 1
+#define QHUFF_SCAN_FIELD_SECTION  0
+#define QHUFF_SCAN_ENCODER_STREAM 1
+
+int qhuff_scan_sections(qhuff_ctx *ctx, const uint8_t *buf,
+                        const uint32_t *sec_off, uint32_t m, unsigned mode,
+                        struct qhuff_literal *lits, uint32_t max_lits,
+                        uint32_t *lit_off, int32_t *rc, uint32_t *consumed,
+                        void *stream);
+
+int qhuff_scan_sections_host(qhuff_ctx *ctx, const uint8_t *buf,
+                             const uint32_t *sec_off, uint32_t m,
+                             unsigned mode, struct qhuff_literal *lits,
+                             uint32_t max_lits, uint32_t *lit_off, int32_t *rc,
+                             uint32_t *consumed);
+
+int qhuff_decode_sections_host(qhuff_ctx *ctx, const uint8_t *buf,
+                               const uint32_t *sec_off, uint32_t m,
+                               unsigned mode, uint32_t max_len,
+                               struct qhuff_literal *lits, uint32_t max_lits,
+                               uint32_t *lit_off, int32_t *rc,
+                               uint32_t *consumed, uint8_t *out,
+                               uint32_t *out_off, uint8_t *status);
+
+int qhuff_scan_sections_cpu(const uint8_t *buf, const uint32_t *sec_off,
+                            uint32_t m, unsigned mode,
+                            struct qhuff_literal *lits, uint32_t max_lits,
+                            uint32_t *lit_off, int32_t *rc,
+                            uint32_t *consumed);
+
 /* ---- field lines and instructions encoded in one launch ------------------
  * qhuff_encode_batch frames every literal of a launch with one prefix width
  * and leaves the instruction bits and the prefixed integers between the
@@ -683,7 +782,7 @@ int qhuff_device_error(qhuff_ctx *ctx);
  * 8 per tile in tile order.  Synchronous. */
 uint64_t qhuff_profile_read(qhuff_ctx *ctx, uint64_t *dst, uint64_t max_words);
 
-/* Launch timing.  With timing on, every encode / decode / hash launch of
+/* Launch timing.  With timing on, every encode / decode / hash / scan launch of
  * the context is dispatched with a pair of HIP events that carry the
  * dispatch's own start and end timestamps (hipExtLaunchKernel: the kernel's
  * device time, what rocprofv3's kernel trace reports, with no timing
@@ -699,6 +798,7 @@ uint64_t qhuff_profile_read(qhuff_ctx *ctx, uint64_t *dst, uint64_t max_words);
 #define QHUFF_KIND_ENCODE 0
 #define QHUFF_KIND_DECODE 1
 #define QHUFF_KIND_HASH   2
+#define QHUFF_KIND_SCAN   3     /* each of qhuff_scan_sections' three launches */
 int qhuff_timing_enable(qhuff_ctx *ctx, int on);
 int qhuff_timing_read(qhuff_ctx *ctx, uint32_t *kind, double *us, uint32_t max);
 

@@ -105,9 +105,17 @@ struct qhuff_ctx
     hipEvent_t *tev;                     // [2 * QHUFF_TIMING_SLOTS], or null
     bool t_on;
     uint32_t t_every;                    // time every t_every-th launch of
-    uint64_t t_seen[3];                  // each kind (launches seen)
+    uint64_t t_seen[4];                  // each kind (launches seen)
     uint64_t t_next, t_first;            // launches timed / first unread
     uint8_t t_kind[QHUFF_TIMING_SLOTS];
+    // qhuff_scan_sections' scratch (counts [cap chunks], then a total per
+    // workgroup of the count launch), allocated at the first scan call; its
+    // launches are ordered across streams as the look-back launches are
+    uint32_t *scan_ws;
+    uint64_t scan_cap;                   // chunks it holds
+    hipEvent_t scan_ev;
+    hipStream_t scan_stream;
+    bool scan_have;
     char err_msg[256];
 };
 

@@ -19,6 +19,7 @@
 
 #include "../../include/qhuff.h"
 #include "qhuff_names.h"
+#include "qhuff_scan_impl.h"
 
 namespace {
 
@@ -292,6 +293,66 @@ qhuff_scan_encoder_stream(const uint8_t *buf, size_t len, uint32_t pos_base,
     *n_lits = s.n;
     *consumed = (size_t) (p - buf);
     return QHUFF_OK;
+}
+
+// ---- the device scan's walker on the host (qhuff_scan_impl.h) --------------
+//
+// qhuff_scan_sections' two passes in plain C++, chunk by chunk: the kernels'
+// walker source over a reader that is the buffer itself.  The scanners above
+// share no code with it.
+
+namespace {
+
+struct HostReader
+{
+    const uint8_t *buf;
+    uint8_t get(uint32_t pos) const { return buf[pos]; }
+};
+
+}  // namespace
+
+extern "C" int
+qhuff_scan_sections_cpu(const uint8_t *buf, const uint32_t *sec_off,
+                        uint32_t m, unsigned mode, struct qhuff_literal *lits,
+                        uint32_t max_lits, uint32_t *lit_off, int32_t *rc,
+                        uint32_t *consumed)
+{
+    if (!lit_off || (mode != QHUFF_SCAN_FIELD_SECTION
+                     && mode != QHUFF_SCAN_ENCODER_STREAM)
+            || (m && (!buf || !sec_off || !rc
+                      || (!consumed && mode == QHUFF_SCAN_ENCODER_STREAM)))
+            || (max_lits && !lits))
+        return QHUFF_EINVAL;
+    for (uint32_t i = 0; i < m; ++i)
+        if (sec_off[i + 1] < sec_off[i])
+            return QHUFF_EINVAL;
+    HostReader r{buf};
+    // the count pass
+    lit_off[0] = 0;
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        qhuff::scan::CountSink s{0};
+        uint32_t used;
+        rc[i] = qhuff::scan::walk_chunk(r, s, mode, sec_off[i], sec_off[i + 1],
+                                        &used);
+        if (consumed)
+            consumed[i] = used;
+        lit_off[i + 1] = lit_off[i] + s.n;
+    }
+    // the write pass
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        const uint32_t first = lit_off[i];
+        const uint32_t last = lit_off[i + 1] < max_lits ? lit_off[i + 1]
+                                                        : max_lits;
+        if (lit_off[i + 1] == first || first >= last)
+            continue;
+        qhuff::scan::WriteSink w{lits, first, last};
+        uint32_t used;
+        (void) qhuff::scan::walk_chunk(r, w, mode, sec_off[i], sec_off[i + 1],
+                                       &used);
+    }
+    return lit_off[m] > max_lits ? QHUFF_ERANGE : QHUFF_OK;
 }
 
 // ---- literal framing from a precomputed payload ---

@@ -392,6 +392,10 @@ qhuff_close(qhuff_ctx *c)
         (void) hipHostFree(c->h_stage);
     if (c->prof)
         (void) hipFree(c->prof);
+    if (c->scan_ws)
+        (void) hipFree(c->scan_ws);
+    if (c->scan_ev)
+        (void) hipEventDestroy(c->scan_ev);
     if (c->tev)
     {
         for (unsigned i = 0; i < 2 * QHUFF_TIMING_SLOTS; ++i)
@@ -661,7 +665,7 @@ qhuff_timing_enable(qhuff_ctx *c, int on)
     }
     c->t_on = on > 0;
     c->t_every = on > 1 ? (uint32_t) on : 1u;
-    c->t_seen[0] = c->t_seen[1] = c->t_seen[2] = 0;
+    c->t_seen[0] = c->t_seen[1] = c->t_seen[2] = c->t_seen[3] = 0;
     c->t_first = c->t_next;
     return QHUFF_OK;
 }
@@ -1047,6 +1051,90 @@ qhuff_decode_wire(qhuff_ctx *c, const uint8_t *buf,
             return launch_wire(a, grid, st, e0, e1);
         });
     });
+}
+
+// ---- field sections and encoder streams scanned (qhuff_scan.hip) -----------
+
+// the scan's scratch for m chunks, and its launches on st ordered behind the
+// scan launches that went out on another stream (one scratch per context)
+static int
+scan_prepare(qhuff_ctx *c, uint32_t m, hipStream_t st)
+{
+    if (!c->scan_ev)
+        HIPCHK(c, hipEventCreateWithFlags(&c->scan_ev, hipEventDisableTiming));
+    if (c->scan_have && st != c->scan_stream)
+    {
+        HIPCHK(c, hipEventRecord(c->scan_ev, c->scan_stream));
+        HIPCHK(c, hipStreamWaitEvent(st, c->scan_ev, 0));
+    }
+    if (m > c->scan_cap)
+    {
+        if (c->scan_ws)
+        {
+            // (earlier scans may still read it)
+            if (c->scan_have)
+                HIPCHK(c, hipStreamSynchronize(c->scan_stream));
+            HIPCHK(c, hipFree(c->scan_ws));
+            c->scan_ws = nullptr;
+            c->scan_cap = 0;
+        }
+        const uint64_t cap = m < 4096 ? 4096 : m;
+        HIPCHK(c, hipMalloc((void **) &c->scan_ws,
+                            4 * (cap + (cap + kScanBlock - 1) / kScanBlock)));
+        c->scan_cap = cap;
+    }
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_scan_sections(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+                    uint32_t m, unsigned mode, struct qhuff_literal *lits,
+                    uint32_t max_lits, uint32_t *lit_off, int32_t *rc,
+                    uint32_t *consumed, void *stream)
+{
+    if (!c || !lit_off || (mode != QHUFF_SCAN_FIELD_SECTION
+                           && mode != QHUFF_SCAN_ENCODER_STREAM)
+            || (m && (!buf || !sec_off || !rc
+                      || (!consumed && mode == QHUFF_SCAN_ENCODER_STREAM)))
+            || (max_lits && !lits))
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(lit_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    if (const int r = scan_prepare(c, m, st))
+        return r;
+    ScanArgs a;
+    a.buf = buf;
+    a.sec_off = sec_off;
+    a.lits = lits;
+    a.lit_off = lit_off;
+    a.rc = rc;
+    a.consumed = consumed;
+    a.cnt = c->scan_ws;
+    a.tot = c->scan_ws + c->scan_cap;
+    a.m = m;
+    a.max_lits = max_lits;
+    a.mode = mode;
+    for (unsigned step = 0; step < 3; ++step)
+    {
+        const int r = timed(c, QHUFF_KIND_SCAN, "launch_scan",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_scan(a, step, st, e0, e1);
+        });
+        // (a launch went out: later scans on another stream wait for it)
+        if (step || !r)
+        {
+            c->scan_stream = st;
+            c->scan_have = true;
+        }
+        if (r)
+            return r;
+    }
+    return QHUFF_OK;
 }
 
 // ---- items encoded in one launch (qhuff_encwire.hip) -----------------------

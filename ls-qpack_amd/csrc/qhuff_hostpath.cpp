@@ -972,6 +972,169 @@ qhuff_decode_wire_host(qhuff_ctx *c, const uint8_t *buf,
     return QHUFF_OK;
 }
 
+// ---- chunks scanned on the device (qhuff_scan_sections) --------------------
+
+// The wire bytes and their offsets up, the scan on the context's stream, the
+// small results (lit_off, rc, consumed) back: the first half of both host
+// forms.  Stage layout: [16 | wire bytes | 16 | sec_off | lit_off | rc | consumed |
+// lits]; the kernels read the caller's offsets unchanged: `buf` rebased by
+// -sec_off[0].  *o_lits: where the descriptors are in the stage, *o_end: the
+// end of the (max_lits) descriptors; `extra` more bytes are kept behind them.
+static int
+scan_staged(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+            uint32_t m, unsigned mode, uint32_t max_lits, uint32_t *lit_off,
+            int32_t *rc, uint32_t *consumed, uint64_t extra, size_t *o_lits,
+            size_t *o_end)
+{
+    const uint64_t a0 = sec_off[0], bytes = (uint64_t) sec_off[m] - a0;
+    const size_t o_so = up16(16 + bytes) + 16;
+    const size_t o_lo = o_so + up16(4ull * (m + 1));
+    const size_t o_rc = o_lo + up16(4ull * (m + 1));
+    const size_t o_co = o_rc + up16(4ull * m);
+    *o_lits = o_co + up16(4ull * m);
+    *o_end = *o_lits + 16ull * max_lits;
+    int r = stage_up(c, *o_end + extra,
+                     {{buf + a0, bytes, 16}, {sec_off, 4ull * (m + 1), o_so}},
+                     o_lo);
+    if (r)
+        return r;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    r = qhuff_scan_sections(c, D + 16 - a0, (const uint32_t *) (D + o_so), m, mode,
+                            (struct qhuff_literal *) (D + *o_lits), max_lits,
+                            (uint32_t *) (D + o_lo), (int32_t *) (D + o_rc),
+                            (uint32_t *) (D + o_co), c->own_stream);
+    if (r)
+        return r;
+    HIPCHK(c, hipMemcpyAsync(H + o_lo, D + o_lo, *o_lits - o_lo,
+                             hipMemcpyDeviceToHost, c->own_stream));
+    HIPCHK(c, hipStreamSynchronize(c->own_stream));
+    memcpy(lit_off, H + o_lo, 4ull * (m + 1));
+    memcpy(rc, H + o_rc, 4ull * m);
+    if (consumed)
+        memcpy(consumed, H + o_co, 4ull * m);
+    return QHUFF_OK;
+}
+
+static bool
+scan_args_ok(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+             uint32_t m, unsigned mode, struct qhuff_literal *lits,
+             uint32_t max_lits, uint32_t *lit_off, int32_t *rc,
+             uint32_t *consumed)
+{
+    if (!c || !lit_off || (mode != QHUFF_SCAN_FIELD_SECTION
+                           && mode != QHUFF_SCAN_ENCODER_STREAM)
+            || (m && (!buf || !sec_off || !rc
+                      || (!consumed && mode == QHUFF_SCAN_ENCODER_STREAM)))
+            || (max_lits && !lits))
+        return false;
+    for (uint32_t i = 0; i < m; ++i)
+        if (sec_off[i + 1] < sec_off[i])
+            return false;
+    return true;
+}
+
+extern "C" int
+qhuff_scan_sections_host(qhuff_ctx *c, const uint8_t *buf,
+                         const uint32_t *sec_off, uint32_t m, unsigned mode,
+                         struct qhuff_literal *lits, uint32_t max_lits,
+                         uint32_t *lit_off, int32_t *rc, uint32_t *consumed)
+{
+    if (!scan_args_ok(c, buf, sec_off, m, mode, lits, max_lits, lit_off, rc,
+                      consumed))
+        return QHUFF_EINVAL;
+    if (m == 0)
+    {
+        lit_off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t o_lits, o_end;
+    int r = scan_staged(c, buf, sec_off, m, mode, max_lits, lit_off, rc,
+                        consumed, 0, &o_lits, &o_end);
+    if (r)
+        return r;
+    const uint32_t n = lit_off[m] < max_lits ? lit_off[m] : max_lits;
+    if (n)
+    {
+        HIPCHK(c, hipMemcpyAsync(c->h_stage + o_lits, c->d_stage + o_lits,
+                                 16ull * n, hipMemcpyDeviceToHost,
+                                 c->own_stream));
+        HIPCHK(c, hipStreamSynchronize(c->own_stream));
+        memcpy(lits, c->h_stage + o_lits, 16ull * n);
+    }
+    return lit_off[m] > max_lits ? QHUFF_ERANGE : QHUFF_OK;
+}
+
+// The whole decode path: scan_staged, then qhuff_decode_wire on the
+// descriptors where the scan left them, then the descriptors, out_off and
+// status in one copy and exactly out_off[n] bytes in another.  Behind the n
+// descriptors the stage holds [out_off | status | out].
+extern "C" int
+qhuff_decode_sections_host(qhuff_ctx *c, const uint8_t *buf,
+                           const uint32_t *sec_off, uint32_t m, unsigned mode,
+                           uint32_t max_len, struct qhuff_literal *lits,
+                           uint32_t max_lits, uint32_t *lit_off, int32_t *rc,
+                           uint32_t *consumed, uint8_t *out, uint32_t *out_off,
+                           uint8_t *status)
+{
+    if (!out_off || !scan_args_ok(c, buf, sec_off, m, mode, lits, max_lits,
+                                  lit_off, rc, consumed)
+            || (max_lits && (!out || !status)))
+        return QHUFF_EINVAL;
+    if (m == 0)
+    {
+        lit_off[0] = 0;
+        out_off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t bytes = (uint64_t) sec_off[m] - sec_off[0];
+    const uint64_t bound = qhuff_decode_bound(bytes, 0);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    // (room for max_lits literals; laid out for the n there are, so that
+    // what comes back is theirs alone)
+    size_t o_lits, o_end;
+    int r = scan_staged(c, buf, sec_off, m, mode, max_lits, lit_off, rc,
+                        consumed, up16(4ull * ((uint64_t) max_lits + 1))
+                                      + up16(max_lits) + up16(bound),
+                        &o_lits, &o_end);
+    if (r)
+        return r;
+    const uint32_t n = lit_off[m];
+    if (n > max_lits)
+    {
+        // as qhuff_scan_sections_host: the first max_lits descriptors
+        if (max_lits)
+        {
+            HIPCHK(c, hipMemcpyAsync(c->h_stage + o_lits, c->d_stage + o_lits,
+                                     16ull * max_lits, hipMemcpyDeviceToHost,
+                                     c->own_stream));
+            HIPCHK(c, hipStreamSynchronize(c->own_stream));
+            memcpy(lits, c->h_stage + o_lits, 16ull * max_lits);
+        }
+        return QHUFF_ERANGE;
+    }
+    const size_t o_oo = o_lits + 16ull * n;
+    const size_t o_st = o_oo + up16(4ull * ((uint64_t) n + 1));
+    const size_t o_out = o_st + up16(n);
+    uint8_t *D = c->d_stage;
+    r = qhuff_decode_wire(c, D + 16 - sec_off[0],
+                          (const struct qhuff_literal *) (D + o_lits), n,
+                          max_len, D + o_out, (uint32_t *) (D + o_oo),
+                          D + o_st, c->own_stream);
+    if (r)
+        return r;
+    if ((r = stage_down(c, o_lits, o_oo, o_out, n, out, out_off)))
+        return r;
+    if (n)
+    {
+        memcpy(lits, c->h_stage + o_lits, 16ull * n);
+        memcpy(status, c->h_stage + o_st, n);
+    }
+    return QHUFF_OK;
+}
+
 // Items encoded in one launch (qhuff_encode_wire): the strings, their
 // offsets and the items go up in one copy; one launch; the offsets come
 // back, then exactly the out_off[n] bytes written.  Nothing is framed or

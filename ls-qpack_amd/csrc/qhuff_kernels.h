@@ -67,6 +67,29 @@ struct WireArgs
     uint32_t max_len;            // 0: no limit
 };
 
+// field sections / encoder streams walked on the device (qhuff_scan.hip):
+// m chunks of buf between sec_off[0 .. m]; cnt (m words) and tot (one word a
+// workgroup of the count launch) are the context's scratch
+constexpr uint32_t kScanBlock = 256;     // chunks (lanes) per workgroup
+constexpr uint32_t kScanTop = 1024;      // totals per round of the top launch
+static inline uint32_t
+scan_blocks(uint32_t m)
+{
+    return (uint32_t) (((uint64_t) m + kScanBlock - 1) / kScanBlock);
+}
+
+struct ScanArgs
+{
+    const uint8_t *buf;
+    const uint32_t *sec_off;
+    ::qhuff_literal *lits;
+    uint32_t *lit_off;
+    int32_t *rc;
+    uint32_t *consumed;          // or null
+    uint32_t *cnt, *tot;
+    uint32_t m, max_lits, mode;
+};
+
 struct HashArgs
 {
     const uint8_t *in;
@@ -199,6 +222,9 @@ int stream_waves_per_block();
 hipError_t launch_wire(const WireArgs &a, uint32_t grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 int wire_waves_per_block();
+// launch `step` of a scan's three (0 count, 1 top, 2 write), m >= 1
+hipError_t launch_scan(const ScanArgs &a, unsigned step, hipStream_t st,
+                       hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // items encoded in one launch (qhuff_encwire.hip): the encode arguments
 // (mode unused: every item has its own framing) and the n items
 hipError_t launch_encwire(const EncArgs &a, const ::qhuff_item *items,

@@ -1,0 +1,274 @@
+// qhuff_scan_impl.h -- the framing walker of qhuff_scan_sections: one chunk
+// of QPACK wire data (a field section, or encoder-stream bytes) walked
+// serially, its literals reported to a sink.
+//
+// The same source runs in two places: as device code, one chunk a lane
+// (qhuff_scan.hip), and as plain C++ on the host (qhuff_scan_sections_cpu,
+// qhuff_frames.cpp, which also builds with g++ alone).  It restates the
+// rules of the host scanners (qhuff_scan_field_section and
+// qhuff_scan_encoder_stream, qhuff_frames.cpp, which stay the independent
+// implementation the tests compare with), i.e. the reference's
+// lsqpack_dec_int / _int24 (lsqpack.c:2372-2460), parse_header_prefix /
+// parse_header_data (lsqpack.c:3955-4046, 3567-3915) and lsqpack_dec_enc_in
+// (lsqpack.c:4574-4960).
+//
+// A walker sees its bytes only through a reader, `uint8_t R::get(uint32_t
+// pos)`, pos an offset into the wire buffer, and asks only for pos inside
+// its own chunk: bytes outside a chunk cannot affect its result.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/qhuff.h"
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define QH_HD __host__ __device__
+#else
+#define QH_HD
+#endif
+
+namespace qhuff {
+namespace scan {
+
+// a literal as the walker found it; offsets into the wire buffer
+struct Lit
+{
+    uint32_t pos, len;
+    uint8_t h, bits, kind, hdr;
+};
+
+QH_HD inline ::qhuff_literal
+descriptor(const Lit &l, uint32_t instr)
+{
+    ::qhuff_literal d;
+    d.pos = l.pos;
+    d.len = l.len;
+    d.huffman = l.h;
+    d.prefix_bits = l.bits;
+    d.kind = l.kind;
+    d.hdr_len = l.hdr;
+    d.instr = instr;
+    return d;
+}
+
+// sinks: put(l, instr) takes the next literal, n counts them; a walker may
+// set n back (an encoder-stream instruction that turns out partial)
+struct CountSink
+{
+    uint32_t n;
+    QH_HD void put(const Lit &, uint32_t) { ++n; }
+};
+
+// descriptors with indices in [n0, limit) are written.  The limit is both
+// max_lits and the end of the chunk's own range: the literal of a partial
+// instruction, counted and then taken back, lies at or past it -- in the
+// next chunk's range, which another lane writes.
+struct WriteSink
+{
+    ::qhuff_literal *lits;
+    uint32_t n, limit;
+    QH_HD void put(const Lit &l, uint32_t instr)
+    {
+        if (n < limit)
+            lits[n] = descriptor(l, instr);
+        ++n;
+    }
+};
+
+// lsqpack_dec_int on a complete buffer [.., end): 0 ok, -1 the buffer ends
+// inside the integer, -2 the value does not fit 64 bits
+template <class R>
+QH_HD inline int
+dec_int(R &r, uint32_t *pp, uint32_t end, unsigned prefix_bits, uint64_t *v_out)
+{
+    uint32_t p = *pp;
+    if (p >= end)
+        return -1;
+    const unsigned pmax = (1u << prefix_bits) - 1;
+    uint64_t v = r.get(p++) & pmax;
+    if (v < pmax)
+    {
+        *pp = p;
+        *v_out = v;
+        return 0;
+    }
+    unsigned M = 0;
+    uint8_t B;
+    do
+    {
+        if (p >= end)
+            return -1;
+        B = r.get(p++);
+        v += (uint64_t) (B & 0x7f) << M;
+        M += 7;
+    } while ((B & 0x80) && M < 64);
+    if (M <= 63 || (M == 70 && B <= 1 && (v & (1ull << 63))))
+    {
+        *pp = p;
+        *v_out = v;
+        return 0;
+    }
+    return -2;
+}
+
+// lsqpack_dec_int24: values >= 2^24 are errors
+template <class R>
+QH_HD inline int
+dec_int24(R &r, uint32_t *pp, uint32_t end, unsigned prefix_bits,
+          uint32_t *v_out)
+{
+    uint64_t v;
+    const int rc = dec_int(r, pp, end, prefix_bits, &v);
+    if (rc)
+        return rc;
+    if (v >= (1u << 24))
+        return -2;
+    *v_out = (uint32_t) v;
+    return 0;
+}
+
+// a string literal whose H bit sits just above its N-bit length prefix;
+// max_len > 0: a declared length above it is an error before the payload is
+// looked for (the field-section rule)
+template <class R, class S>
+QH_HD inline int
+literal(R &r, S &s, uint32_t *pp, uint32_t end, unsigned prefix_bits,
+        unsigned kind, uint32_t instr, uint32_t max_len)
+{
+    uint32_t p = *pp;
+    if (p >= end)
+        return -1;
+    const uint32_t start = p;
+    Lit l;
+    l.h = (uint8_t) ((r.get(p) >> prefix_bits) & 1);
+    const int rc = dec_int24(r, &p, end, prefix_bits, &l.len);
+    if (rc)
+        return rc;
+    if (max_len && l.len > max_len)
+        return -2;
+    if (end - p < l.len)
+        return -1;
+    l.pos = p;
+    l.bits = (uint8_t) prefix_bits;
+    l.kind = (uint8_t) kind;
+    l.hdr = (uint8_t) (p - start);
+    s.put(l, instr);
+    *pp = p + l.len;
+    return 0;
+}
+
+// one complete field section in [p, end): 0, -1 (ends inside a line) or -2
+template <class R, class S>
+QH_HD inline int
+walk_field_section(R &r, S &s, uint32_t p, uint32_t end)
+{
+    const uint32_t max_str = QHUFF_MAX_STRLEN;
+    uint64_t v;
+    int rc;
+    // section prefix: Required Insert Count (8-bit prefix), S + Delta Base
+    // (7-bit prefix)
+    if ((rc = dec_int(r, &p, end, 8, &v)) || (rc = dec_int(r, &p, end, 7, &v)))
+        return rc;
+    while (p < end)
+    {
+        const uint8_t b = r.get(p);
+        const uint32_t at = p;
+        uint32_t idx;
+        if (b & 0x80)                          // 1Txxxxxx indexed field line
+            rc = dec_int24(r, &p, end, 6, &idx);
+        else if (b & 0x40)                     // 01NTxxxx literal, name ref
+        {
+            rc = dec_int24(r, &p, end, 4, &idx);
+            if (!rc)
+                rc = literal(r, s, &p, end, 7, QHUFF_LIT_VALUE, at, max_str);
+        }
+        else if (b & 0x20)                     // 001NHxxx literal name
+        {
+            rc = literal(r, s, &p, end, 3, QHUFF_LIT_NAME, at, max_str);
+            if (!rc)
+                rc = literal(r, s, &p, end, 7, QHUFF_LIT_VALUE, at, max_str);
+        }
+        else if (b & 0x10)                     // 0001xxxx indexed post-base
+            rc = dec_int24(r, &p, end, 4, &idx);
+        else                                   // 0000Nxxx post-base name ref
+        {
+            rc = dec_int24(r, &p, end, 3, &idx);
+            if (!rc)
+                rc = literal(r, s, &p, end, 7, QHUFF_LIT_VALUE, at, max_str);
+        }
+        if (rc)
+            return rc;
+    }
+    return 0;
+}
+
+// encoder-stream bytes in [p, end): 0 with *stop the end of the last
+// complete instruction (a partial one is left, its literals taken back), or
+// -2
+template <class R, class S>
+QH_HD inline int
+walk_encoder_stream(R &r, S &s, uint32_t p, uint32_t end, uint32_t *stop)
+{
+    while (p < end)
+    {
+        uint32_t q = p;
+        const uint8_t b = r.get(q);
+        const uint32_t n0 = s.n;
+        uint32_t v;
+        int rc;
+        if (b & 0x80)                // 1Txxxxxx insert with name reference
+        {
+            rc = dec_int24(r, &q, end, 6, &v);
+            if (!rc)
+                rc = literal(r, s, &q, end, 7, QHUFF_LIT_VALUE, p, 0);
+        }
+        else if (b & 0x40)           // 01Hxxxxx insert with literal name
+        {
+            rc = literal(r, s, &q, end, 5, QHUFF_LIT_NAME, p, 0);
+            if (!rc)
+                rc = literal(r, s, &q, end, 7, QHUFF_LIT_VALUE, p, 0);
+        }
+        else                         // 001xxxxx capacity / 000xxxxx dup
+        {
+            uint64_t w;
+            rc = dec_int(r, &q, end, 5, &w);
+            if (!rc && !(b & 0x20) && w >= (1u << 24))
+                rc = -2;
+        }
+        if (rc == -1)
+        {
+            s.n = n0;
+            break;
+        }
+        if (rc)
+            return rc;
+        p = q;
+    }
+    *stop = p;
+    return 0;
+}
+
+// One chunk [a, b) in `mode`: its QHUFF_* result and its consumed bytes;
+// the sink's n has advanced by the chunk's literals, or is back where it
+// was when the result is not QHUFF_OK.
+template <class R, class S>
+QH_HD inline int
+walk_chunk(R &r, S &s, unsigned mode, uint32_t a, uint32_t b,
+           uint32_t *consumed)
+{
+    const uint32_t n0 = s.n;
+    uint32_t stop = b;
+    const int rc = mode == QHUFF_SCAN_FIELD_SECTION
+                       ? walk_field_section(r, s, a, b)
+                       : walk_encoder_stream(r, s, a, b, &stop);
+    if (rc)
+    {
+        s.n = n0;
+        *consumed = 0;
+        return rc == -1 ? QHUFF_ETRUNC : QHUFF_EPROTO;
+    }
+    *consumed = stop - a;
+    return QHUFF_OK;
+}
+
+}  // namespace scan
+}  // namespace qhuff

@@ -49,6 +49,8 @@ EXPORTS = (
     "qhuff_grid_waves",
     "qhuff_encode_wire_bound", "qhuff_items_check", "qhuff_encode_wire",
     "qhuff_encode_wire_host",
+    "qhuff_scan_sections", "qhuff_scan_sections_host",
+    "qhuff_decode_sections_host", "qhuff_scan_sections_cpu",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -57,6 +59,8 @@ EXPORTS = (
 EPROTO, ETRUNC = -71, -61
 TIMING_SLOTS = 256                        # QHUFF_TIMING_SLOTS
 KIND_ENCODE, KIND_DECODE, KIND_HASH = 0, 1, 2
+KIND_SCAN = 3                             # qhuff_scan_sections' three launches
+SCAN_FIELD_SECTION, SCAN_ENCODER_STREAM = 0, 1    # QHUFF_SCAN_*
 LIT_NAME, LIT_VALUE = 1, 2
 MAX_STRLEN = 65535                        # QHUFF_MAX_STRLEN (LSXPACK_MAX_STRLEN)
 
@@ -294,6 +298,22 @@ def lib():
         L.qhuff_encode_wire_host.restype = C.c_int
         L.qhuff_encode_wire_host.argtypes = [vp, vp, u32p, vp, C.c_uint32, vp,
                                              u32p]
+        i32p = C.c_void_p
+        L.qhuff_scan_sections.restype = C.c_int
+        L.qhuff_scan_sections.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint,
+                                          vp, C.c_uint32, vp, vp, vp, vp]
+        L.qhuff_scan_sections_host.restype = C.c_int
+        L.qhuff_scan_sections_host.argtypes = [vp, vp, u32p, C.c_uint32,
+                                               C.c_uint, vp, C.c_uint32, u32p,
+                                               i32p, u32p]
+        L.qhuff_decode_sections_host.restype = C.c_int
+        L.qhuff_decode_sections_host.argtypes = [vp, vp, u32p, C.c_uint32,
+                                                 C.c_uint, C.c_uint32, vp,
+                                                 C.c_uint32, u32p, i32p, u32p,
+                                                 vp, u32p, vp]
+        L.qhuff_scan_sections_cpu.restype = C.c_int
+        L.qhuff_scan_sections_cpu.argtypes = [vp, u32p, C.c_uint32, C.c_uint,
+                                              vp, C.c_uint32, u32p, i32p, u32p]
         _lib = L
     return _lib
 
@@ -396,6 +416,39 @@ def scan_encoder_stream(buf, pos_base=0):
     rc, lits = _scan(lib().qhuff_scan_encoder_stream, bytes(buf), pos_base,
                      C.byref(consumed))
     return rc, lits, consumed.value
+
+
+def _sections_host_args(buf, sec_off, max_lits):
+    """the host forms' arrays: (buf, sec_off, m, max_lits, lits, lit_off, rc,
+    consumed)"""
+    import numpy as np
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    sec_off = np.ascontiguousarray(sec_off, dtype=np.uint32)
+    m = len(sec_off) - 1
+    return (buf, sec_off, m, max_lits,
+            np.zeros(16 * max(max_lits, 1), dtype=np.uint8),
+            np.zeros(m + 1, dtype=np.uint32), np.zeros(max(m, 1), dtype=np.int32),
+            np.zeros(max(m, 1), dtype=np.uint32))
+
+
+def scan_sections_cpu(buf, sec_off, mode=SCAN_FIELD_SECTION, max_lits=None):
+    """qhuff_scan_sections_cpu: the device scan's walker run on the host over
+    chunks buf[sec_off[i] : sec_off[i + 1]] -> (ret, lits, lit_off, rc,
+    consumed): ret OK or ERANGE (lit_off[-1] > max_lits), lits the uint8
+    array of the min(lit_off[-1], max_lits) descriptors written.  max_lits
+    None: a first call with room for none counts them."""
+    if max_lits is None:
+        max_lits = int(scan_sections_cpu(buf, sec_off, mode, 0)[2][-1])
+    buf, sec_off, m, max_lits, lits, lit_off, rc, consumed = \
+        _sections_host_args(buf, sec_off, max_lits)
+    ret = lib().qhuff_scan_sections_cpu(
+        _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off), m, mode,
+        _np_ptr(lits), max_lits, _np_ptr(lit_off), _np_ptr(rc),
+        _np_ptr(consumed))
+    if ret not in (OK, ERANGE):
+        raise QhuffError("qhuff_scan_sections_cpu failed: %d" % ret)
+    n = min(int(lit_off[-1]), max_lits)
+    return ret, lits[:16 * n], lit_off, rc[:m], consumed[:m]
 
 
 def literals_array(lits):
@@ -966,6 +1019,98 @@ class Codec:
         self._check(rc, "qhuff_decode_wire_host")
         return ([out[out_off[i]:out_off[i + 1]].tobytes() for i in range(n)],
                 status[:n])
+
+    # field sections and encoder streams scanned on the device ---------------
+    def scan_sections_into(self, buf, sec_off, m, mode, lits, max_lits,
+                           lit_off, rc, consumed, stream=None):
+        """qhuff_scan_sections: all device tensors (consumed may be None in
+        field-section mode); lits holds 16 * max_lits bytes."""
+        r = lib().qhuff_scan_sections(
+            self._ctx, buf.data_ptr(), sec_off.data_ptr(), m, mode,
+            lits.data_ptr() if lits is not None else None, max_lits,
+            lit_off.data_ptr(), rc.data_ptr(),
+            consumed.data_ptr() if consumed is not None else None,
+            self._stream(stream))
+        self._check(r, "qhuff_scan_sections")
+
+    def scan_sections(self, buf, sec_off, mode=SCAN_FIELD_SECTION,
+                      max_lits=None, stream=None):
+        """buf: uint8 cuda tensor of wire bytes; sec_off: int32 cuda tensor
+        [m+1].  Returns device tensors (lits uint8 [16 * max_lits], lit_off
+        int32 [m+1], rc int32 [m], consumed int32 [m]); lit_off[m] is the
+        full count, to be compared with max_lits.  max_lits None: a first
+        scan with room for no descriptor counts them (it waits for that
+        count: two scans and a synchronisation; a caller that knows a bound
+        passes it)."""
+        import torch
+        m = sec_off.numel() - 1
+        dev = buf.device
+        if max_lits is None:
+            lit_off = torch.empty(m + 1, dtype=torch.int32, device=dev)
+            rc = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+            consumed = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+            self.scan_sections_into(buf, sec_off, m, mode, None, 0, lit_off,
+                                    rc, consumed, stream)
+            (stream or torch.cuda.current_stream()).synchronize()
+            max_lits = int(lit_off[m].item()) & 0xFFFFFFFF
+        lits = torch.empty(16 * max(max_lits, 1), dtype=torch.uint8, device=dev)
+        lit_off = torch.empty(m + 1, dtype=torch.int32, device=dev)
+        rc = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        consumed = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        self.scan_sections_into(buf, sec_off, m, mode, lits, max_lits,
+                                lit_off, rc, consumed, stream)
+        return lits, lit_off, rc[:m], consumed[:m]
+
+    def scan_sections_host(self, buf, sec_off, mode=SCAN_FIELD_SECTION,
+                           max_lits=None):
+        """qhuff_scan_sections_host over host arrays -> (ret, lits, lit_off,
+        rc, consumed) as scan_sections_cpu (max_lits None: a first call
+        with room for none counts them)."""
+        if max_lits is None:
+            max_lits = int(self.scan_sections_host(buf, sec_off, mode,
+                                                   0)[2][-1])
+        buf, sec_off, m, max_lits, lits, lit_off, rc, consumed = \
+            _sections_host_args(buf, sec_off, max_lits)
+        ret = lib().qhuff_scan_sections_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, mode, _np_ptr(lits), max_lits, _np_ptr(lit_off),
+            _np_ptr(rc), _np_ptr(consumed))
+        if ret != ERANGE:
+            self._check(ret, "qhuff_scan_sections_host")
+        n = min(int(lit_off[-1]), max_lits)
+        return ret, lits[:16 * n], lit_off, rc[:m], consumed[:m]
+
+    def decode_sections_host(self, buf, sec_off, mode=SCAN_FIELD_SECTION,
+                             max_len=None, max_lits=None):
+        """qhuff_decode_sections_host: scan and decode in one call -> (ret,
+        lits, lit_off, rc, consumed, out, out_off, status); ret OK, or ERANGE
+        (lit_off[-1] > max_lits: nothing decoded, the first max_lits
+        descriptors, out / out_off / status None).  max_lits None:
+        scan_sections_host counts the literals first (one more round trip;
+        the context's stage grows with max_lits, so a caller passes the
+        count or a bound near it, not a loose one)."""
+        import numpy as np
+        if max_lits is None:
+            max_lits = int(self.scan_sections_host(buf, sec_off, mode,
+                                                   0)[2][-1])
+        buf, sec_off, m, max_lits, lits, lit_off, rc, consumed = \
+            _sections_host_args(buf, sec_off, max_lits)
+        wire = max(int(sec_off[-1]) - int(sec_off[0]), 0)
+        out = np.zeros(decode_bound(wire, 0), dtype=np.uint8)
+        out_off = np.zeros(max_lits + 1, dtype=np.uint32)
+        status = np.zeros(max(max_lits, 1), dtype=np.uint8)
+        ret = lib().qhuff_decode_sections_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, mode, max_len or 0, _np_ptr(lits), max_lits, _np_ptr(lit_off),
+            _np_ptr(rc), _np_ptr(consumed),
+            _np_ptr(out), _np_ptr(out_off), _np_ptr(status))
+        if ret == ERANGE:
+            return (ret, lits[:16 * max_lits], lit_off, rc[:m], consumed[:m],
+                    None, None, None)
+        self._check(ret, "qhuff_decode_sections_host")
+        n = int(lit_off[-1])
+        return (ret, lits[:16 * n], lit_off, rc[:m], consumed[:m],
+                out[:out_off[n]], out_off[:n + 1], status[:n])
 
     # field lines and instructions encoded in one launch ---------------------
     def encode_wire_into(self, data, in_off, items, n, out, out_off,
