@@ -136,23 +136,6 @@ struct Packer
     }
 };
 
-// HPACK prefixed-integer byte count (lsqpack_val2len, lsqpack.c:767-783)
-__device__ __forceinline__ uint32_t
-int_len(uint32_t v, uint32_t prefix)
-{
-    uint32_t mask = (1u << prefix) - 1;
-    if (v < mask)
-        return 1;
-    v -= mask;
-    uint32_t n = 2;
-    while (v >= 128)
-    {
-        v >>= 7;
-        ++n;
-    }
-    return n;
-}
-
 // valid-byte mask (4 bits) of dword d for a string [rs, re), re > rs
 __device__ __forceinline__ uint32_t
 byte_mask(uint32_t d, uint32_t d0, uint32_t dl, uint32_t rs, uint32_t re)
@@ -324,30 +307,75 @@ pack_bits(const QH_LDS uint32_t *in, uint32_t rs, uint32_t re, bool raw,
     return pos;
 }
 
+// HPACK prefixed-integer byte count (lsqpack_val2len, lsqpack.c:767-783)
+__device__ __forceinline__ uint32_t
+int_len(uint32_t v, uint32_t prefix)
+{
+    uint32_t mask = (1u << prefix) - 1;
+    if (v < mask)
+        return 1;
+    v -= mask;
+    uint32_t n = 2;
+    while (v >= 128)
+    {
+        v >>= 7;
+        ++n;
+    }
+    return n;
+}
+
+// The byte sinks of put_int.  StageBytes: the byte OR-ed into the zeroed LDS
+// stage at bit `pos`, which moves on; PackBytes: the byte to a Packer.
+struct StageBytes
+{
+    QH_LDS uint32_t *st;
+    uint32_t pos;
+    __device__ __forceinline__ void put(uint32_t b)
+    {
+        or_bits(st, pos, b, 8);
+        pos += 8;
+    }
+};
+template <class Sink>
+struct PackBytes
+{
+    Packer<Sink> *pk;
+    __device__ __forceinline__ void put(uint32_t b) { pk->put(b, 8); }
+};
+
+// The HPACK prefixed integer (lsqpack_enc_int, lsqpack.c:787-814), written
+// here and nowhere else: v on a prefix of `prefix` bits of a first byte
+// preset to `first` (its prefix bits clear), then 7-bit groups, low ones
+// first, each but the last with the continuation bit; int_len() bytes.  The
+// sink goes in by value and comes back (a StageBytes: its position).
+template <class Bytes>
+__device__ __forceinline__ Bytes
+put_int(Bytes s, uint32_t first, uint32_t prefix, uint32_t v)
+{
+    const uint32_t mask = (1u << prefix) - 1;
+    if (v < mask)
+    {
+        s.put(first | v);
+        return s;
+    }
+    s.put(first | mask);
+    v -= mask;
+    while (v >= 128)
+    {
+        s.put(0x80 | (v & 0x7f));
+        v >>= 7;
+    }
+    s.put(v);
+    return s;
+}
+
 // literal framing (lsqpack.c:852-854, 862-864, 819-836): H bit + the length
-// as an HPACK integer with a `mode`-bit prefix, at bit `pos`; returns the
-// position after it
+// on a `mode`-bit prefix, at bit `pos`; returns the position after it
 __device__ __forceinline__ uint32_t
 emit_prefix(QH_LDS uint32_t *st, uint32_t pos, uint32_t mode, bool huff,
             uint32_t plen)
 {
-    const uint32_t mask = (1u << mode) - 1, first = huff ? (1u << mode) : 0;
-    if (plen < mask)
-    {
-        or_bits(st, pos, first | plen, 8);
-        return pos + 8;
-    }
-    or_bits(st, pos, first | mask, 8);
-    pos += 8;
-    uint32_t v = plen - mask;
-    while (v >= 128)
-    {
-        or_bits(st, pos, 0x80 | (v & 0x7f), 8);
-        pos += 8;
-        v >>= 7;
-    }
-    or_bits(st, pos, v, 8);
-    return pos + 8;
+    return put_int(StageBytes{st, pos}, huff ? 1u << mode : 0u, mode, plen).pos;
 }
 
 // literal framing + payload + EOS-prefix padding into the LDS stage, from
@@ -364,35 +392,6 @@ emit_bits(const QH_LDS uint32_t *in, uint32_t rs, uint32_t re, uint32_t mode,
     const uint32_t pad = (8 - (pos & 7)) & 7;
     if (pad)
         or_bits(st, pos, (1u << pad) - 1, pad);
-}
-
-// literal framing (lsqpack.c:852-854, 862-864, 819-836): H bit + prefixed
-// length, then the payload (slow path, straight to global memory)
-template <class Src, class Sink>
-__device__ __forceinline__ void
-emit_string(const Src &src, uint32_t rs, uint32_t re, uint32_t mode,
-            bool huff, uint32_t plen, const QH_LDS u32x2 *s_enc,
-            Packer<Sink> &pk)
-{
-    if (mode)
-    {
-        uint32_t mask = (1u << mode) - 1, first = huff ? (1u << mode) : 0;
-        if (plen < mask)
-            pk.put(first | plen, 8);
-        else
-        {
-            pk.put(first | mask, 8);
-            uint32_t v = plen - mask;
-            while (v >= 128)
-            {
-                pk.put(0x80 | (v & 0x7f), 8);
-                v >>= 7;
-            }
-            pk.put(v, 8);
-        }
-    }
-    pack_string(src, rs, re, !huff, s_enc, pk);
-    pk.finish();
 }
 
 // per-string sizing result
@@ -421,12 +420,51 @@ size_from_bits(uint32_t mode, uint32_t bits, uint32_t len)
     return z;
 }
 
-template <class Src>
+// A lane's frame: what stands around its payload where the lane codes its
+// string by itself (size_string, emit_string, enc_tile_sizes, enc_slow_tile).
+//   size(bits, len)  its literal, of `bits` Huffman bits or len raw bytes
+//   front()          its bytes in front of the literal
+//   payload()        whether it has a literal at all
+//   head(bytes, z)   the bytes in front of the payload, by put_int
+// StrFrame, the batch's: a literal on a prefix of `mode` bits (lsqpack.c:
+// 852-854, 862-864, 819-836: H bit + length), or with mode 0 the payload
+// alone.  ItemFrame (qhuff_encwire_impl.h) is an item's.
+struct StrFrame
+{
+    uint32_t mode;
+    __device__ __forceinline__ EncSize size(uint32_t bits, uint32_t len) const
+    {
+        return size_from_bits(mode, bits, len);
+    }
+    __device__ __forceinline__ uint32_t front() const { return 0; }
+    __device__ __forceinline__ bool payload() const { return true; }
+    template <class Bytes>
+    __device__ __forceinline__ void head(Bytes s, const EncSize &z) const
+    {
+        if (mode)
+            put_int(s, z.huff ? 1u << mode : 0u, mode, z.plen);
+    }
+};
+
+template <class Frame, class Src>
 __device__ __forceinline__ EncSize
-size_string(uint32_t mode, const Src &src, uint32_t rs, uint32_t re,
+size_string(const Frame &fr, const Src &src, uint32_t rs, uint32_t re,
             const QH_LDS uint8_t *s_len)
 {
-    return size_from_bits(mode, code_bits(src, rs, re, s_len), re - rs);
+    return fr.size(fr.payload() ? code_bits(src, rs, re, s_len) : 0u, re - rs);
+}
+
+// a lane's whole output straight to global memory (slow path): the frame's
+// head, the payload, the EOS-prefix padding (lsqpack.c:5171-5189)
+template <class Frame, class Src, class Sink>
+__device__ __forceinline__ void
+emit_string(const Frame &fr, const Src &src, uint32_t rs, uint32_t re,
+            const EncSize &z, const QH_LDS u32x2 *s_enc, Packer<Sink> &pk)
+{
+    fr.head(PackBytes<Sink>{&pk}, z);
+    if (fr.payload())
+        pack_string(src, rs, re, !z.huff, s_enc, pk);
+    pk.finish();
 }
 
 // ---- byte-parallel dense pass ------------------------------------------------
@@ -800,32 +838,30 @@ emit_dense(const QH_LDS uint32_t *in, uint32_t rs, uint32_t re, uint32_t mode,
     return p0;
 }
 
-// A tile whose input or output does not fit the stages, coded eagerly:
-// sizes from the stage (given) or from global memory, then packed straight
-// to global memory.  The tile's output base comes from base_of(total) (the
-// batch kernel's look-back, or the service's running offset); its offsets go
-// to t_off (the tile's first string).  Returns base + total.  Out of line
-// (cold), state by value.
-template <class SM, class BaseOf>
+// A tile whose input or output does not fit the stages, coded eagerly: its
+// sizes given (sz, z: from the stage, or from enc_tile_sizes) or, with
+// sized = false and the input past the stage, taken here from global
+// memory; then every lane's output (frame fr) packed straight to global
+// memory, from the stage when the input is there.  The tile's output base
+// comes from base_of(total) (the batch kernels' look-back, or the service's
+// running offset); its offsets go to t_off (the tile's first string).
+// Returns base + total.  Out of line (cold), state by value.
+template <class SM, class Frame, class Offs, class BaseOf>
 __device__ __noinline__ uint64_t
-enc_slow_tile(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
-              QH_LDS EncWave *wv, uint32_t rs, uint32_t re, EncSize z,
-              uint32_t cnt, TileOffs to, Span sp, uint32_t sz, bool sized,
-              uint8_t *out, uint32_t *t_off, BaseOf base_of)
+enc_slow_tile(const uint8_t *in, Frame fr, QH_LDS SM *sm, QH_LDS EncWave *wv,
+              EncSize z, uint32_t cnt, Offs to, Span sp, uint32_t sz,
+              bool sized, uint8_t *out, uint32_t *t_off, BaseOf base_of)
 {
     const bool valid = lane_id() < cnt;
     const EncGlb gsrc{(const QH_GLB uint32_t *) sp.pa};
-    if (!sp.staged)
+    const uint32_t rs = valid ? (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa) : 0;
+    const uint32_t re = valid ? (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa) : 0;
+    if (!sp.staged && !sized)
     {
-        rs = valid ? (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa) : 0;
-        re = valid ? (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa) : 0;
-        if (!sized)
-        {
-            z = (EncSize){0, 0, true};
-            if (valid)
-                z = size_string(mode, gsrc, rs, re, sm->len);
-            sz = z.size;
-        }
+        z = (EncSize){0, 0, true};
+        if (valid)
+            z = size_string(fr, gsrc, rs, re, sm->len);
+        sz = valid ? fr.front() + z.size : 0u;
     }
     const SlowTile f = SlowTile::begin(sz, base_of);
     if (valid && sz)
@@ -836,21 +872,19 @@ enc_slow_tile(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
         const uint32_t p0 = adj + (uint32_t) f.base + f.excl;
         pk.init(p0, p0 + sz);
         if (sp.staged)
-            emit_string(EncLds{wv->in}, rs, re, mode, z.huff, z.plen, sm->enc,
-                        pk);
+            emit_string(fr, EncLds{wv->in}, rs, re, z, sm->enc, pk);
         else
-            emit_string(gsrc, rs, re, mode, z.huff, z.plen, sm->enc, pk);
+            emit_string(fr, gsrc, rs, re, z, sm->enc, pk);
     }
     return f.end<false>(cnt, 0, t_off, nullptr);
 }
 
-
 // the sizes of a tile past the stage, from global memory (as enc_slow_tile
 // sizes them with sized = false)
-template <class SM>
+template <class SM, class Frame, class Offs>
 __device__ __noinline__ EncSize
-enc_tile_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm, uint32_t cnt,
-               TileOffs to, Span sp)
+enc_tile_sizes(const uint8_t *in, Frame fr, QH_LDS SM *sm, uint32_t cnt,
+               Offs to, Span sp)
 {
     EncSize z = (EncSize){0, 0, true};
     if (lane_id() < cnt)
@@ -858,7 +892,7 @@ enc_tile_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm, uint32_t cnt,
         const EncGlb gsrc{(const QH_GLB uint32_t *) sp.pa};
         const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
         const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
-        z = size_string(mode, gsrc, rs, re, sm->len);
+        z = size_string(fr, gsrc, rs, re, sm->len);
     }
     return z;
 }
@@ -873,38 +907,33 @@ enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
 #endif
               );
 
-// the encode side of the wave pipeline (qhuff_pipeline.h, qhuff_service.hip);
-// SM: the workgroup's LDS (enc, mt, len)
-template <class SM, bool Full = true>
-struct EncPolicyT
+// What the two policies of the encode family state once (EncPolicyT here,
+// EncWirePolicyT in qhuff_encwire_impl.h): the stage constants, the wave's
+// LDS, the staged chunks and the dense pass over them, a lane's range of the
+// dense stream and the zeroed output stage.  SM: the workgroup's LDS (enc,
+// mt, len).
+template <class SM>
+struct EncStagePolicy
 {
     static constexpr bool kStatus = false;
-    // Full: big tiles through output slots, long payloads copied by the
-    // wave (see DecPolicyT)
-    static constexpr bool kBig = Full;
     static constexpr bool kCoop = false;          // (no coop_phase)
     static constexpr uint64_t coop = 0;
     static constexpr int kInCap = kEncInCap;
-    static constexpr int kDepth = QH_ENC_DEPTH;       // pending tiles
     static constexpr int kOutCap = kEncOutCap;
     static constexpr int kNch = kChunks;          // 16-byte chunks per lane
-    static constexpr uint32_t kTS = kWT;          // strings per tile
-    using Offs = TileOffs;
+    static constexpr uint32_t kTS = kWT;          // strings (items) per tile
     const uint8_t *in;
-    uint32_t mode;                   // 0 payload, 3/5/7 literal prefix bits
     QH_LDS SM *sm;
     QH_LDS EncWave *wv;
-    uint32_t rs, re;                 // this lane's string in the stage
-    uint32_t ds, bits;               // its range of the dense stream
-    EncSize z;
     uint32_t dense;                  // wave-uniform: tile from the dense stream
 #ifdef QH_PATH_TRACE
     PathTrace tr;                    // (diagnostic) the current tile's paths
 #endif
 
     // staged tile: chunks into the LDS stage
-    __device__ __forceinline__ void stage_in(const Chunks<kChunks> &ch,
-                                             const Span &sp, const TileOffs &)
+    template <class Offs>
+    __device__ __forceinline__ void stage_in(const Chunks<kNch> &ch,
+                                             const Span &sp, const Offs &)
     {
         ch.store<false>((QH_LDS u32x4 *) wv->in, sp.n16);
     }
@@ -922,6 +951,69 @@ struct EncPolicyT
     {
         return wv->out;
     }
+    // This lane's range (ds, bits) of the dense stream, for lanes [lo, cnt)
+    // of a prepared span: string i spans the dense bits between the offsets
+    // of its ends (an item without a literal too: its bytes shift the
+    // others').  re: where this lane's string ends in the span sp.  Clears
+    // `dense` when the stream has overflown.
+    template <class Offs>
+    __device__ __forceinline__ void dense_range(const Offs &to, const Span &sp,
+                                                uint32_t re, uint32_t lo,
+                                                uint32_t cnt, uint32_t &ds,
+                                                uint32_t &bits)
+    {
+        if (dense)
+        {
+            const uint32_t se = dense_at(wv, re);
+            const uint32_t ra = (uint32_t) ((uintptr_t) (in + read_lane(to.o0, lo))
+                                            - sp.pa);
+            const uint32_t s_first = dense_at(wv, ra);
+            uint32_t prev = wave_shr1(se);
+            // (every lane shifts: not moved into the select's branch)
+            asm volatile("" : "+v"(prev));
+            ds = lane_id() != lo ? prev : s_first;
+            bits = se - ds;
+            dense = read_lane(se, cnt - 1) + 64 <= kDenseBits;
+        }
+#ifdef QH_PATH_TRACE
+        tr.units += 1;
+        tr.dense += dense ? 1u : 0u;
+#endif
+    }
+    // `total` bytes of the output stage zeroed: emit ORs its bits in
+    __device__ __forceinline__ void zero_out(uint32_t total)
+    {
+        QH_LDS u32x4 *o4 = (QH_LDS u32x4 *) wv->out;
+        const uint32_t n16 = (total + 15) / 16 + 1;
+        for (uint32_t i = lane_id(); i < n16; i += 64)
+            o4[i] = (u32x4){0, 0, 0, 0};
+        wave_sync();
+    }
+};
+
+// the encode side of the wave pipeline (qhuff_pipeline.h, qhuff_service.hip)
+template <class SM, bool Full = true>
+struct EncPolicyT : EncStagePolicy<SM>
+{
+    using Base = EncStagePolicy<SM>;
+    using Base::in;
+    using Base::sm;
+    using Base::wv;
+    using Base::dense;
+    using Base::kTS;
+#ifdef QH_PATH_TRACE
+    using Base::tr;
+#endif
+    // Full: big tiles through output slots, long payloads copied by the
+    // wave (see DecPolicyT)
+    static constexpr bool kBig = Full;
+    static constexpr int kDepth = QH_ENC_DEPTH;       // pending tiles
+    using Offs = TileOffs;
+    uint32_t mode;                   // 0 payload, 3/5/7 literal prefix bits
+    uint32_t rs, re;                 // this lane's string in the stage
+    uint32_t ds, bits;               // its range of the dense stream
+    EncSize z;
+
     // staged tile: size this lane's string (E1, and the E3 choice)
     __device__ __forceinline__ void codec(const TileOffs &to, uint32_t cnt,
                                           const Span &sp, uint32_t *sz,
@@ -944,27 +1036,11 @@ struct EncPolicyT
         rs = valid ? (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa) : 0;
         re = valid ? (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa) : 0;
         z = (EncSize){0, 0, true};
-        if (dense)
-        {
-            // string i spans the dense bits between the offsets of its ends
-            const uint32_t se = dense_at(wv, re);
-            const uint32_t ra = (uint32_t) ((uintptr_t) (in + read_lane(to.o0, lo))
-                                            - sp.pa);
-            const uint32_t s_first = dense_at(wv, ra);
-            uint32_t prev = wave_shr1(se);
-            // (every lane shifts: not moved into the select's branch)
-            asm volatile("" : "+v"(prev));
-            ds = lane != lo ? prev : s_first;
-            bits = se - ds;
-            dense = read_lane(se, cnt - 1) + 64 <= kDenseBits;
-        }
-#ifdef QH_PATH_TRACE
-        tr.units += 1;
-        tr.dense += dense ? 1u : 0u;
-#endif
+        this->dense_range(to, sp, re, lo, cnt, ds, bits);
         if (valid)
             z = dense ? size_from_bits(mode, bits, re - rs)
-                      : size_string(mode, EncLds{wv->in}, rs, re, sm->len);
+                      : size_string(StrFrame{mode}, EncLds{wv->in}, rs, re,
+                                    sm->len);
         *sz = z.size;
         *st = 0;
     }
@@ -972,11 +1048,7 @@ struct EncPolicyT
     __device__ __forceinline__ void emit(uint32_t excl, uint32_t sz,
                                          uint32_t total)
     {
-        QH_LDS u32x4 *o4 = (QH_LDS u32x4 *) wv->out;
-        const uint32_t n16 = (total + 15) / 16 + 1;
-        for (uint32_t i = lane_id(); i < n16; i += 64)
-            o4[i] = (u32x4){0, 0, 0, 0};
-        wave_sync();
+        this->zero_out(total);
 #ifdef QH_TIME_NO_EMIT                       // timing builds only: no output
         return;
 #endif
@@ -1020,7 +1092,6 @@ struct EncPolicyT
                       excl);
     }
 
-    // a tile of the batch kernel: base from the look-back
     // a big tile's sizes, and its output into dst when it fits
     __device__ __forceinline__ bool big_sizes(uint32_t cnt, TileOffs to, Span sp,
                                               uint32_t &sz, uint32_t &st,
@@ -1033,17 +1104,18 @@ struct EncPolicyT
 #endif
                              );
     }
-    // a big tile whose output does not fit a slot (qhuff_pipeline.h), after
-    // the pending tiles are flushed: base from the look-back
     // the sizes of a tile past the stage (the lean kernel: no codec ran)
     __device__ __forceinline__ void slow_size(uint32_t cnt, TileOffs to, Span sp,
                                               uint32_t &sz, uint32_t &st)
     {
-        z = enc_tile_sizes(in, mode, sm, cnt, to, sp);
+        z = enc_tile_sizes(in, StrFrame{mode}, sm, cnt, to, sp);
         sz = z.size;
         st = 0;
     }
-    // ... its output once the look-back lb (aggregate published) resolves
+    // a tile out of line (the lean kernel's, or a full kernel's big tile
+    // whose output does not fit a slot), after the pending tiles are
+    // flushed: its output once the look-back lb (aggregate published)
+    // resolves
     __device__ __forceinline__ void slow_tile(Coord c, uint32_t t, uint32_t cnt,
                                               TileOffs to, Span sp, uint32_t sz,
                                               uint32_t, bool sized, uint8_t *out,
@@ -1052,10 +1124,10 @@ struct EncPolicyT
     {
         // sized: z from slow_size (the lean kernel) -- a full kernel's big
         // tile has its sizes from big_sizes but not z, so it sizes again
-        const uint64_t end = enc_slow_tile(in, mode, sm, wv, rs, re, z, cnt,
-                                              to, sp, sz, sized, out,
-                                              out_off + (uint64_t) t * kTS,
-                                              StartedBase{c, lb});
+        const uint64_t end = enc_slow_tile(in, StrFrame{mode}, sm, wv, z, cnt,
+                                           to, sp, sz, sized, out,
+                                           out_off + (uint64_t) t * kTS,
+                                           StartedBase{c, lb});
         last_tile_end(c, t, end, out_off, n);
     }
     // a tile at a known base
@@ -1065,8 +1137,8 @@ struct EncPolicyT
                                                      uint8_t *out, uint32_t *t_off,
                                                      uint8_t *)
     {
-        return enc_slow_tile(in, mode, sm, wv, rs, re, z, cnt, to, sp, sz, false,
-                                out, t_off, FixedBase{base});
+        return enc_slow_tile(in, StrFrame{mode}, sm, wv, z, cnt, to, sp, sz,
+                             false, out, t_off, FixedBase{base});
     }
 };
 
@@ -1090,7 +1162,8 @@ enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
               )
 {
     using P = EncPolicyT<SM, true>;
-    P pol{in, mode, sm, wv};
+    P pol{{in, sm, wv, false}, mode};
+    const StrFrame fr{mode};
     const uint32_t lane = lane_id();
     const bool valid = lane < cnt;
     // per-lane packing of lanes [lo, hi) from the LDS stage (span su) at
@@ -1100,14 +1173,13 @@ enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
         {
             const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - su.pa);
             const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - su.pa);
-            const EncSize z = size_string(mode, EncLds{wv->in}, rs, re, sm->len);
+            const EncSize z = size_string(fr, EncLds{wv->in}, rs, re, sm->len);
             if (z.size)
             {
                 Packer<PackGlb> pk;
                 pk.sink.out = dst;
                 pk.init(at, at + z.size);
-                emit_string(EncLds{wv->in}, rs, re, mode, z.huff, z.plen,
-                            sm->enc, pk);
+                emit_string(fr, EncLds{wv->in}, rs, re, z, sm->enc, pk);
             }
         }
     };
@@ -1137,7 +1209,7 @@ enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
             EncSize z = (EncSize){0, 0, true};
             if (lane == i0)
             {
-                z = size_string(mode, src, rs, re, sm->len);
+                z = size_string(fr, src, rs, re, sm->len);
                 sz = z.size;
             }
             const uint32_t n = read_lane(sz, i0);
@@ -1150,7 +1222,7 @@ enc_big_sizes(const uint8_t *in, uint32_t mode, QH_LDS SM *sm,
                 Packer<PackGlb> pk;
                 pk.sink.out = dst;
                 pk.init(run, run + n);
-                emit_string(src, rs, re, mode, z.huff, z.plen, sm->enc, pk);
+                emit_string(fr, src, rs, re, z, sm->enc, pk);
             }
             run += n;
             i0 += 1;

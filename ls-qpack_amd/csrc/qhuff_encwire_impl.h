@@ -1,8 +1,10 @@
 // qhuff_encwire_impl.h -- whole QPACK field lines and instructions encoded
 // in one launch (qhuff_encode_wire, include/qhuff.h).  See
-// qhuff_encwire.hip.  Here: the item loads, the prefixed integer, the
-// out-of-line tile and the tile policy; the dense pass, sizing, the bit
-// packers and the literal framing are qhuff_encode_impl.h's, unchanged.
+// qhuff_encwire.hip.  Here: the item loads, an item's frame (ItemFrame) and
+// the tile policy.  Everything else is qhuff_encode_impl.h's: the stage
+// policy (EncStagePolicy), the dense pass, sizing, the bit packers, the one
+// writer of prefixed integers (put_int, into the LDS stage or a Packer) and
+// the out-of-line tile (enc_tile_sizes, enc_slow_tile, over the frame).
 #pragma once
 
 #include <stddef.h>
@@ -99,166 +101,48 @@ struct ItemOffs
     __device__ __forceinline__ uint32_t last() const { return read_lane(o1, 63); }
 };
 
-// the item's size: its integer, and its literal as size_from_bits /
-// size_string frame it with the lane's own prefix width (none: nothing)
-__device__ __forceinline__ EncSize
-item_size_bits(uint32_t m, uint32_t bits, uint32_t len)
+// An item's frame (qhuff_encode_impl.h, StrFrame): the integer on its own
+// first byte, then the literal on a prefix of str_bits bits with str_first
+// on its first byte; without str_bits no literal, whatever the string.
+struct ItemFrame
 {
-    EncSize z = (EncSize){0, 0, true};
-    if (im_sb(m))
-        z = size_from_bits(im_sb(m), bits, len);
-    return z;
-}
-
-template <class Src>
-__device__ __forceinline__ EncSize
-item_size_string(uint32_t m, const Src &src, uint32_t rs, uint32_t re,
-                 const QH_LDS uint8_t *s_len)
-{
-    EncSize z = (EncSize){0, 0, true};
-    if (im_sb(m))
-        z = size_string(im_sb(m), src, rs, re, s_len);
-    return z;
-}
-
-// lsqpack_enc_int (lsqpack.c:787-814) into the zeroed LDS stage at byte
-// `start`: the value on a prefix of im_ib(m) bits of a first byte preset to
-// int_first
-__device__ __forceinline__ void
-emit_int(QH_LDS uint32_t *st, uint32_t start, uint32_t m, uint32_t v)
-{
-    const uint32_t mask = (1u << im_ib(m)) - 1;
-    uint32_t pos = 8 * start;
-    if (v < mask)
+    uint32_t m, ival;                // item_meta, the integer's value
+    __device__ __forceinline__ EncSize size(uint32_t bits, uint32_t len) const
     {
-        or_bits(st, pos, im_ifirst(m) | v, 8);
-        return;
+        EncSize z = (EncSize){0, 0, true};
+        if (im_sb(m))
+            z = size_from_bits(im_sb(m), bits, len);
+        return z;
     }
-    or_bits(st, pos, im_ifirst(m) | mask, 8);
-    pos += 8;
-    v -= mask;
-    while (v >= 128)
+    __device__ __forceinline__ uint32_t front() const { return im_ilen(m); }
+    __device__ __forceinline__ bool payload() const { return im_sb(m) != 0; }
+    template <class Bytes>
+    __device__ __forceinline__ void head(Bytes s, const EncSize &z) const
     {
-        or_bits(st, pos, 0x80 | (v & 0x7f), 8);
-        pos += 8;
-        v >>= 7;
+        if (im_ib(m))
+            s = put_int(s, im_ifirst(m), im_ib(m), ival);
+        if (const uint32_t sb = im_sb(m))
+            put_int(s, im_sfirst(m) | (z.huff ? 1u << sb : 0u), sb, z.plen);
     }
-    or_bits(st, pos, v, 8);
-}
-
-// an item straight to global memory (the out-of-line tile): the integer,
-// then the literal as emit_string frames it with str_first on its first byte
-template <class Src, class Sink>
-__device__ __forceinline__ void
-emit_item(const Src &src, uint32_t rs, uint32_t re, uint32_t m, uint32_t ival,
-          const EncSize &z, const QH_LDS u32x2 *s_enc, Packer<Sink> &pk)
-{
-    if (im_ib(m))
-    {
-        const uint32_t mask = (1u << im_ib(m)) - 1;
-        uint32_t v = ival;
-        if (v < mask)
-            pk.put(im_ifirst(m) | v, 8);
-        else
-        {
-            pk.put(im_ifirst(m) | mask, 8);
-            v -= mask;
-            while (v >= 128)
-            {
-                pk.put(0x80 | (v & 0x7f), 8);
-                v >>= 7;
-            }
-            pk.put(v, 8);
-        }
-    }
-    if (const uint32_t sb = im_sb(m))
-    {
-        const uint32_t mask = (1u << sb) - 1;
-        const uint32_t first = im_sfirst(m) | (z.huff ? 1u << sb : 0u);
-        if (z.plen < mask)
-            pk.put(first | z.plen, 8);
-        else
-        {
-            pk.put(first | mask, 8);
-            uint32_t v = z.plen - mask;
-            while (v >= 128)
-            {
-                pk.put(0x80 | (v & 0x7f), 8);
-                v >>= 7;
-            }
-            pk.put(v, 8);
-        }
-        pack_string(src, rs, re, !z.huff, s_enc, pk);
-    }
-    pk.finish();
-}
-
-// the sizes of a tile past the stage, from global memory
-template <class SM>
-__device__ __noinline__ EncSize
-encwire_tile_sizes(const uint8_t *in, QH_LDS SM *sm, uint32_t cnt, ItemOffs to,
-                   uint32_t m, Span sp)
-{
-    EncSize z = (EncSize){0, 0, true};
-    if (lane_id() < cnt)
-    {
-        const EncGlb gsrc{(const QH_GLB uint32_t *) sp.pa};
-        const uint32_t rs = (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa);
-        const uint32_t re = (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa);
-        z = item_size_string(m, gsrc, rs, re, sm->len);
-    }
-    return z;
-}
-
-// A tile whose input or output does not fit the stages, as enc_slow_tile():
-// sized already (sz, z: from the stage, or encwire_tile_sizes), every item
-// packed straight to global memory by its lane -- from the stage when the
-// input is there, else from global memory.  Out of line (cold).
-template <class SM, class BaseOf>
-__device__ __noinline__ uint64_t
-encwire_slow_tile(const uint8_t *in, QH_LDS SM *sm, QH_LDS EncWave *wv,
-                  EncSize z, uint32_t m, uint32_t ival, uint32_t cnt,
-                  ItemOffs to, Span sp,
-                  uint32_t sz, uint8_t *out, uint32_t *t_off, BaseOf base_of)
-{
-    const bool valid = lane_id() < cnt;
-    const uint32_t rs = valid ? (uint32_t) ((uintptr_t) (in + to.o0) - sp.pa) : 0;
-    const uint32_t re = valid ? (uint32_t) ((uintptr_t) (in + to.o1) - sp.pa) : 0;
-    const SlowTile f = SlowTile::begin(sz, base_of);
-    if (valid && sz)
-    {
-        const uint32_t adj = (uint32_t) ((uintptr_t) out & 3);
-        Packer<PackGlb> pk;
-        pk.sink.out = out - adj;
-        const uint32_t p0 = adj + (uint32_t) f.base + f.excl;
-        pk.init(p0, p0 + sz);
-        if (sp.staged)
-            emit_item(EncLds{wv->in}, rs, re, m, ival, z, sm->enc, pk);
-        else
-            emit_item(EncGlb{(const QH_GLB uint32_t *) sp.pa}, rs, re, m,
-                      ival, z, sm->enc, pk);
-    }
-    return f.end<false>(cnt, 0, t_off, nullptr);
-}
+};
 
 // the item side of the wave pipeline (qhuff_pipeline.h): a lean policy over
-// the encode stages -- EncPolicyT<SM, false> with the framing per lane
+// the encode stages (EncStagePolicy) with the framing per lane
 template <class SM>
-struct EncWirePolicyT
+struct EncWirePolicyT : EncStagePolicy<SM>
 {
-    static constexpr bool kStatus = false;
+    using Base = EncStagePolicy<SM>;
+    using Base::in;
+    using Base::sm;
+    using Base::wv;
+    using Base::dense;
+    using Base::kTS;
+#ifdef QH_PATH_TRACE
+    using Base::tr;
+#endif
     static constexpr bool kBig = false;
-    static constexpr bool kCoop = false;
-    static constexpr uint64_t coop = 0;
-    static constexpr int kInCap = kEncInCap;
     static constexpr int kDepth = QH_ENCW_DEPTH;
-    static constexpr int kOutCap = kEncOutCap;
-    static constexpr int kNch = kChunks;
-    static constexpr uint32_t kTS = kWT;          // items per tile
     using Offs = ItemOffs;
-    const uint8_t *in;
-    QH_LDS SM *sm;
-    QH_LDS EncWave *wv;
     uint32_t rse;                    // this lane's string in the stage:
                                      // start | end << 16 (<= 3 KB)
     uint32_t dsb;                    // its range of the dense stream:
@@ -266,32 +150,15 @@ struct EncWirePolicyT
     uint32_t m, ival;                // its item (item_meta; the item's
                                      // second dword until codec())
     EncSize z;                       // its literal
-    uint32_t dense;                  // wave-uniform: tile from the dense stream
-#ifdef QH_PATH_TRACE
-    PathTrace tr;                    // (diagnostic) the current tile's paths
-#endif
 
     // staged tile: chunks into the LDS stage; the tile's items on their way
-    __device__ __forceinline__ void stage_in(const Chunks<kChunks> &ch,
+    __device__ __forceinline__ void stage_in(const Chunks<Base::kNch> &ch,
                                              const Span &sp, const Offs &to)
     {
-        ch.store<false>((QH_LDS u32x4 *) wv->in, sp.n16);
+        Base::stage_in(ch, sp, to);
         const u32x2 v = item_load(to.s0, to.cnt);
         ival = v.x;
         m = v.y;
-    }
-    // the byte-parallel pass over the staged span, as the batch kernel's
-    __device__ __forceinline__ void prepare(const Span &sp)
-    {
-        if constexpr (SM::kMtRep)
-            dense_pass<true>(sp.n16, sm->mtr, wv);
-        else
-            dense_pass<false>(sp.n16, sm->mt, wv);
-        dense = true;
-    }
-    __device__ __forceinline__ const QH_LDS uint32_t *out_stage() const
-    {
-        return wv->out;
     }
     // staged tile: size this lane's item
     __device__ __forceinline__ void codec(const Offs &to, uint32_t cnt,
@@ -305,29 +172,13 @@ struct EncWirePolicyT
         rse = rs | (re << 16);
         m = valid ? item_meta(m, ival) : 0u;
         z = (EncSize){0, 0, true};
-        uint32_t bits = 0;
-        if (dense)
-        {
-            // string i spans the dense bits between the offsets of its ends
-            // (an item without a literal too: its bytes shift the others')
-            const uint32_t se = dense_at(wv, re);
-            const uint32_t ra = (uint32_t) ((uintptr_t) (in + to.first()) - sp.pa);
-            const uint32_t s_first = dense_at(wv, ra);
-            uint32_t prev = wave_shr1(se);
-            // (every lane shifts: not moved into the select's branch)
-            asm volatile("" : "+v"(prev));
-            const uint32_t ds = lane != 0 ? prev : s_first;
-            bits = se - ds;
-            dense = read_lane(se, cnt - 1) + 64 <= kDenseBits;
-            dsb = ds | (bits << 16);
-        }
-#ifdef QH_PATH_TRACE
-        tr.units += 1;
-        tr.dense += dense ? 1u : 0u;
-#endif
+        uint32_t ds = 0, bits = 0;
+        this->dense_range(to, sp, re, 0, cnt, ds, bits);
+        dsb = ds | (bits << 16);
         if (valid)
-            z = dense ? item_size_bits(m, bits, re - rs)
-                      : item_size_string(m, EncLds{wv->in}, rs, re, sm->len);
+            z = dense ? ItemFrame{m, ival}.size(bits, re - rs)
+                      : size_string(ItemFrame{m, ival}, EncLds{wv->in}, rs, re,
+                                    sm->len);
         *sz = im_ilen(m) + z.size;
         *st = 0;
     }
@@ -336,14 +187,10 @@ struct EncWirePolicyT
     __device__ __forceinline__ void emit(uint32_t excl, uint32_t sz,
                                          uint32_t total)
     {
-        QH_LDS u32x4 *o4 = (QH_LDS u32x4 *) wv->out;
-        const uint32_t n16 = (total + 15) / 16 + 1;
-        for (uint32_t i = lane_id(); i < n16; i += 64)
-            o4[i] = (u32x4){0, 0, 0, 0};
-        wave_sync();
+        this->zero_out(total);
         (void) sz;
         if (im_ib(m))
-            emit_int(wv->out, excl, m, ival);
+            put_int(StageBytes{wv->out, 8 * excl}, im_ifirst(m), im_ib(m), ival);
         const uint32_t sb = im_sb(m);
         if (!sb)
             return;
@@ -365,7 +212,7 @@ struct EncWirePolicyT
         const u32x2 v = item_load(to.s0, cnt);
         ival = v.x;
         m = lane_id() < cnt ? item_meta(v.y, v.x) : 0u;
-        z = encwire_tile_sizes(in, sm, cnt, to, m, sp);
+        z = enc_tile_sizes(in, ItemFrame{m, ival}, sm, cnt, to, sp);
         sz = im_ilen(m) + z.size;
         st = 0;
     }
@@ -376,10 +223,11 @@ struct EncWirePolicyT
                                               uint32_t *out_off, uint8_t *,
                                               uint64_t n, const LookBack &lb)
     {
-        const uint64_t end = encwire_slow_tile(in, sm, wv, z, m, ival, cnt, to, sp,
-                                               sz, out,
-                                               out_off + (uint64_t) t * kTS,
-                                               StartedBase{c, lb});
+        // (sized: by codec() or slow_size())
+        const uint64_t end = enc_slow_tile(in, ItemFrame{m, ival}, sm, wv, z,
+                                           cnt, to, sp, sz, true, out,
+                                           out_off + (uint64_t) t * kTS,
+                                           StartedBase{c, lb});
         last_tile_end(c, t, end, out_off, n);
     }
 };

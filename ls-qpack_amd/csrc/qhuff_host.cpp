@@ -872,7 +872,7 @@ qhuff_encode_batch(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
 {
     if (!c || !in_off || !out_off || (n && (!in || !out)))
         return QHUFF_EINVAL;
-    if (mode != 0 && mode != 3 && mode != 5 && mode != 7)
+    if (!mode_ok(mode))
         return QHUFF_EINVAL;
     hipStream_t st = (hipStream_t) stream;
     const uint64_t wpb = (uint64_t) encode_waves_per_block();

@@ -3,11 +3,14 @@ integer, on each path that frames them (no GPU).
 
 A QPACK literal is H bit + length (an HPACK integer on a 3-, 5- or 7-bit
 prefix) + payload.  The kernels size that header in one place (int_len,
-size_from_bits) and write it in others: emit_prefix into the out stage
-(emit_bits, emit_dense, the encode_wire policy), emit_string straight to
-global memory (pack_lds from the stage, enc_slow_tile from the stage or from
-global memory), emit_int / emit_item for encode_wire's integers.  A one-off
-in one of them at one boundary moves every later byte of its tile.
+size_from_bits) and write it, and encode_wire's integers, in one other:
+put_int, through one of two byte sinks.  StageBytes ORs the byte into the
+out stage (emit_prefix for emit_bits and emit_dense, the encode_wire
+policy's integer); PackBytes hands it to the global bit packer (emit_string:
+pack_lds from the stage, enc_slow_tile from the stage or from global memory,
+with the batch's frame or the item's).  What differs from path to path is
+the sink and the first byte and prefix width its caller passes; a slip there
+at one boundary still moves every later byte of its tile.
 
 cases(): for each prefix, payloads of mask - 1, mask, mask + 127, mask + 128,
 mask + 16383 and mask + 16384 bytes (headers of 1, 2, 2, 3, 3 and 4 bytes),

@@ -10,7 +10,8 @@ through qhuff_encode_batch (default, lean and full kernels, three paddings,
 and mode 0 as the control), its host form (staged and registered), the
 two-context host form cut inside the fixture tiles, the service one fixture
 tile a call, qhuff_encode_wire and its host form for the 16 KB literals
-behind an integer, four strings of 2 MB for the header's fifth byte, and the
+behind an integer and for the boundary integers on the tiles off the dense
+path, four strings of 2 MB for the header's fifth byte, and the
 literals read back where the encoder put them by qhuff_decode_wire.
 Everything is compared with the oracle, bytes and offsets.
 """
@@ -133,8 +134,8 @@ def int_only(nbytes):
 
 def ordinary_items(rng, n):
     """integers on both sides of every boundary on every prefix width, each
-    with a short literal behind it: tiles of the dense path (emit_int,
-    emit_prefix)"""
+    with a short literal behind it: tiles of the dense path (put_int into
+    the out stage, for the integer and through emit_prefix)"""
     strs, its = [], []
     for i in range(n):
         ib = 1 + i % 8
@@ -200,6 +201,66 @@ def test_wire_batches(p):
     seen = {(it.int_bits, len(Q.enc_int(0, it.ival, it.int_bits)))
             for it in b.items[:L.TS]}
     assert seen >= {(ib, k) for ib in range(1, 9) for k in (1, 2, 3, 4)}
+
+
+WIRE_PATHS = ("in", "out", "lane")       # encode_wire's tiles off the dense path
+CYCLE = 48                               # ordinary_items: 8 widths x 6 values
+
+
+def _forced_tile(rng, path, r):
+    """one tile on `path`: an integer-only item of r bytes, ordinary_items'
+    whole cycle, what forces the path, the tuner, nothing up to 64"""
+    strs, its = ordinary_items(rng, CYCLE)
+    if path == "in":
+        # one string that passes the stage alone: every item from global memory
+        strs.append(F._tokens(rng, 3100))
+        its.append(item(str_bits=7))
+    elif path == "out":
+        # raw literals: 2880 bytes and their headers, 120 bytes of integers
+        # (staged: 2976 bytes of input and at most 30 around them)
+        strs = [F._raw(rng, 60) for _ in its]
+        strs += [F._tokens(rng, 16) for _ in range(6)]
+        its += [item(str_bits=7)] * 6
+    else:
+        # 24 strings of 40 30-bit codes: 28800 dense bits of the 24640
+        strs = [bytes(rng.choice(L.B30) for _ in range(40)) if i & 1 else s
+                for i, s in enumerate(strs)]
+    strs, its = _tuned([b""] + strs, [int_only(r)] + its)
+    fill = L.TS - len(strs)
+    return strs + [b""] * fill, its + [item()] * fill
+
+
+@functools.lru_cache(maxsize=None)
+def wire_path_batch(r):
+    """a dense tile, one tile on each of WIRE_PATHS with every integer of the
+    cycle r bytes past a dword of the output, a dense tile -> Batch"""
+    rng = random.Random(170 + r)
+    strs, its = _tuned(*ordinary_items(rng, L.TS - 1))
+    for path in WIRE_PATHS:
+        s, i = _forced_tile(rng, path, r)
+        strs, its = strs + s, its + i
+    s2, i2 = ordinary_items(rng, L.TS)
+    return WireBatch(strs + s2, its + i2)
+
+
+@pytest.mark.parametrize("r", range(4))
+def test_wire_path_batches(r):
+    """every integer boundary on every prefix width on each encode_wire path
+    off the dense one, at output residue r"""
+    b = wire_path_batch(r)
+    assert b.n == 5 * L.TS
+    for res in range(16):
+        assert b.paths(res) == ["dense"] + list(WIRE_PATHS) + ["dense"], res
+    full = {(ib, k) for ib in range(1, 9) for k in (1, 2, 3, 4)}
+    for j, path in enumerate(WIRE_PATHS, 1):
+        t0 = j * L.TS
+        assert int(b.want_off[t0]) % 4 == 0 and len(b.want[t0]) == r
+        cyc = b.items[t0 + 1:t0 + 1 + CYCLE]
+        seen = {(it.int_bits, len(Q.enc_int(0, it.ival, it.int_bits)))
+                for it in cyc}
+        assert seen >= full, (path, sorted(full - seen))
+        assert {it.str_bits for it in cyc} == set(F.PREFIXES)
+        assert int(b.want_off[t0 + 1]) % 4 == r
 
 
 # ---- GPU ---------------------------------------------------------------------------
@@ -301,6 +362,15 @@ def test_encode_wire_long_literals(codec, p):
     out, oo = check_both(codec, b)
     for i, c, ilen in where:
         assert out[oo[i] + ilen:oo[i + 1]] == framed(c, allowed_first(p))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("r", range(4))
+def test_encode_wire_integers_off_the_dense_path(codec, r):
+    """qhuff_encode_wire and its host form: the integers of the cycle on the
+    tiles coded out of line (from global memory, from the stage) and on the
+    tile packed item per lane, on every start residue"""
+    check_both(codec, wire_path_batch(r))
 
 
 @pytest.mark.gpu
