@@ -716,6 +716,125 @@ int qhuff_encode_wire_host(qhuff_ctx *ctx, const uint8_t *in,
                            const struct qhuff_item *items, uint32_t n,
                            uint8_t *out, uint32_t *out_off);
 
+/* ---- header lists encoded to field sections against the static table ------
+ * qhuff_encode_wire writes field lines once somebody has decided, per header,
+ * which form the line takes.  That decision is the first thing
+ * lsqpack_enc_encode does for every header (lsqpack.c:1671-1715, 1835-1866,
+ * 1904-1930): hash the name, hash the value seeded with the name's hash, probe
+ * nameval2id_plus_one / name2id_plus_one (lsqpack.c:629-666, 721-764), compare
+ * the bytes.  Whenever the dynamic table is not used -- LQEF_NO_DYN, an
+ * encoder of capacity 0, a LSXPACK_NEVER_INDEX header that is not in the
+ * dynamic table -- it is per header and stateless, and the line is one of
+ *   QHUFF_LINE_INDEXED  EHA_INDEXED_STAT (lsqpack.c:2033-2039): name and value
+ *                       are a static entry; 0xC0 | id on a 6-bit prefix
+ *   QHUFF_LINE_NAMEREF  EHA_LIT_WITH_NAME_STAT (2110-2125): only the name is;
+ *                       0x50 | N << 5, id on a 4-bit prefix, then
+ *                       lsqpack_enc_enc_str(7, value)
+ *   QHUFF_LINE_LITERAL  EHA_LIT (2061-2076): neither; 0x20 | N << 4 +
+ *                       lsqpack_enc_enc_str(3, name), then
+ *                       lsqpack_enc_enc_str(7, value)
+ * (N: the header is never to be indexed), behind the field-section prefix
+ * 00 00 (lsqpack.c:1277, 1296).  QHUFF_FEATURE_ENCODE_HEADERS and the symbols
+ * announce it (the ABI version is unchanged).
+ *
+ * Headers are laid out as for qhuff_xxh32_headers: off[2n + 1], header i is
+ * name in[off[2i] .. off[2i+1]) and value in[off[2i+1] .. off[2i+2]).
+ *
+ * qhuff_static_lookup -- per header the two hashes (those of
+ * qhuff_xxh32_headers with seed QHUFF_XXH_SEED; name_hash / nameval_hash may
+ * each be NULL), kind[i] = QHUFF_LINE_* and static_id[i] = the static index the
+ * reference finds (find_in_static_full, else lsqpack_find_in_static_headers;
+ * of several entries with one name the lowest), QHUFF_STATIC_NONE for
+ * LITERAL.  One launch, timed as QHUFF_KIND_HASH.  Device pointers,
+ * asynchronous on `stream`.  A stateful caller copies the results into its
+ * lsxpack_header (name_hash, nameval_hash, qpack_index and the flags
+ * LSXPACK_NAME_HASH | LSXPACK_NAMEVAL_HASH | LSXPACK_QPACK_IDX (|
+ * LSXPACK_VAL_MATCHED)) and lsqpack_enc_encode skips its own hashing and,
+ * by the line, its static probes (lsqpack.c:1672-1694, 1836-1840): both for
+ * an INDEXED header, lsqpack_find_in_static_headers but not
+ * find_in_static_full for a NAMEREF one, none for a LITERAL one
+ * (INTEGRATION.md).
+ * qhuff_static_lookup_host: host pointers, synchronous, one staged round trip.
+ * qhuff_static_lookup_cpu: the kernel's lookup source run on the host over
+ * host pointers: no context and no device call (a diagnostic, as
+ * qhuff_scan_sections_cpu).  QHUFF_EINVAL for a null pointer, QHUFF_ERANGE
+ * for n above 2^31 - 1.
+ * qhuff_static_probe_tables (diagnostic, host only): the library's two probe
+ * tables, 512 bytes each, id + 1 or 0, as it builds them from the static
+ * table with its own XXH32.
+ *
+ * qhuff_encode_headers -- m field sections; section s holds the headers
+ * [sec_hdr[s], sec_hdr[s+1]), sec_hdr[0] = 0, sec_hdr[m] = n, non-decreasing.
+ * hflags[i] bit 0 (QHUFF_HDR_NEVER_INDEX) is the N bit of header i; hflags
+ * may be NULL (all 0).  Output: the sections back to back, each its two
+ * prefix bytes and its lines -- the bytes lsqpack_enc_start_header /
+ * lsqpack_enc_encode(..., flags | LQEF_NO_DYN) / lsqpack_enc_end_header write
+ * for it; an empty section is its two prefix bytes -- section s in
+ * out[sec_out[s] .. sec_out[s+1]), sec_out[0] = 0; kind[n] and static_id[n] as
+ * qhuff_static_lookup's, each may be NULL.  LSXPACK_QPACK_IDX on input is out
+ * of scope.  `out` must hold qhuff_encode_headers_bound(in_bytes, n, m) =
+ * qhuff_encode_wire_bound(in_bytes, 2n + 2m) bytes.
+ *
+ * Launches on `stream`: the lookup (QHUFF_KIND_HASH), which also writes
+ * 2n + 2m items and their string offsets into scratch of the context -- two
+ * per section prefix, two per header -- then qhuff_encode_wire's launch
+ * unchanged on those arrays (QHUFF_KIND_ENCODE), then a gather of sec_out from
+ * the items' offsets.  The names of INDEXED and NAMEREF lines still pass
+ * through the encode kernel's stage although no literal is made of them; that
+ * is accepted.  Scratch, 16 bytes an item, belongs to the context: allocated at
+ * the first call, grown on demand, ordered across streams as the scan's.
+ *
+ * The buffer contract above applies.  Writes: out[0 .. sec_out[m]),
+ * sec_out[0 .. m], kind and static_id (n bytes each), nothing else; for
+ * n = m = 0 only sec_out[0].  Reads: off[0 .. 2n], sec_hdr[0 .. m], hflags and
+ * the 16-byte-aligned blocks that contain in[off[0] .. off[2n]).
+ * qhuff_encode_headers: device pointers, asynchronous; sec_hdr is in device
+ * memory where the call cannot check it: its form is THE CALLER'S DUTY.
+ * QHUFF_EINVAL for a null pointer.  qhuff_encode_headers_host: host pointers,
+ * synchronous -- one upload, the launches, then sec_out, the optional byte
+ * arrays and exactly sec_out[m] bytes come back; no loop over the headers on
+ * the host but the offsets' check.  QHUFF_EINVAL for a null pointer, decreasing
+ * off or sec_hdr, sec_hdr[0] != 0 or sec_hdr[m] != n; QHUFF_ERANGE when
+ * 2n + 2m or the bound passes 32 bits. */
+#define QHUFF_FEATURE_ENCODE_HEADERS 1
+#define QHUFF_HDR_NEVER_INDEX 1     /* hflags[i] bit 0: LQEF_NEVER_INDEX /
+                                       LSXPACK_NEVER_INDEX                  */
+#define QHUFF_LINE_INDEXED 0        /* EHA_INDEXED_STAT                     */
+#define QHUFF_LINE_NAMEREF 1        /* EHA_LIT_WITH_NAME_STAT               */
+#define QHUFF_LINE_LITERAL 2        /* EHA_LIT                              */
+#define QHUFF_STATIC_NONE  0xFF
+
+int qhuff_static_lookup(qhuff_ctx *ctx, const uint8_t *in, const uint32_t *off,
+                        uint32_t n, uint32_t *name_hash,
+                        uint32_t *nameval_hash, uint8_t *kind,
+                        uint8_t *static_id, void *stream);
+
+int qhuff_static_lookup_host(qhuff_ctx *ctx, const uint8_t *in,
+                             const uint32_t *off, uint32_t n,
+                             uint32_t *name_hash, uint32_t *nameval_hash,
+                             uint8_t *kind, uint8_t *static_id);
+
+int qhuff_static_lookup_cpu(const uint8_t *in, const uint32_t *off, uint32_t n,
+                            uint32_t *name_hash, uint32_t *nameval_hash,
+                            uint8_t *kind, uint8_t *static_id);
+
+int qhuff_static_probe_tables(uint8_t name2id_plus_one[512],
+                              uint8_t nameval2id_plus_one[512]);
+
+uint64_t qhuff_encode_headers_bound(uint64_t in_bytes, uint32_t n, uint32_t m);
+
+int qhuff_encode_headers(qhuff_ctx *ctx, const uint8_t *in,
+                         const uint32_t *off, uint32_t n,
+                         const uint8_t *hflags, const uint32_t *sec_hdr,
+                         uint32_t m, uint8_t *out, uint32_t *sec_out,
+                         uint8_t *kind, uint8_t *static_id, void *stream);
+
+int qhuff_encode_headers_host(qhuff_ctx *ctx, const uint8_t *in,
+                              const uint32_t *off, uint32_t n,
+                              const uint8_t *hflags, const uint32_t *sec_hdr,
+                              uint32_t m, uint8_t *out, uint32_t *sec_out,
+                              uint8_t *kind, uint8_t *static_id);
+
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman
  * payload was precomputed by a QHUFF_ENC_PAYLOAD batch (huff, huff_len =

@@ -116,6 +116,15 @@ struct qhuff_ctx
     hipEvent_t scan_ev;
     hipStream_t scan_stream;
     bool scan_have;
+    // qhuff_encode_headers' scratch for hdr_cap items (2n + 2m of a call):
+    // the items [8 * cap], their string offsets [cap + 1] and their output
+    // offsets [cap + 1], each part 16-byte aligned; allocated at the first
+    // call, ordered across streams as scan_ws is
+    uint8_t *hdr_ws;
+    uint64_t hdr_cap;                    // items it holds
+    hipEvent_t hdr_ev;
+    hipStream_t hdr_stream;
+    bool hdr_have;
     char err_msg[256];
 };
 

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "../../include/qhuff.h"
+#include "qhuff_lookup_impl.h"
 #include "qhuff_names.h"
 #include "qhuff_scan_impl.h"
 
@@ -353,6 +354,61 @@ qhuff_scan_sections_cpu(const uint8_t *buf, const uint32_t *sec_off,
                                        &used);
     }
     return lit_off[m] > max_lits ? QHUFF_ERANGE : QHUFF_OK;
+}
+
+// ---- the lookup kernel's source on the host (qhuff_lookup_impl.h) -----------
+//
+// qhuff_static_lookup in plain C++, header by header: the kernels' XXH32 and
+// lookup source over a reader that is the buffer itself, against this
+// translation unit's copy of the static table and its probe tables.
+
+namespace {
+
+constexpr qhuff::StaticTable kStaticHost = qhuff::make_static_table();
+
+}  // namespace
+
+extern "C" int
+qhuff_static_lookup_cpu(const uint8_t *in, const uint32_t *off, uint32_t n,
+                        uint32_t *name_hash, uint32_t *nameval_hash,
+                        uint8_t *kind, uint8_t *static_id)
+{
+    if (!off || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    for (uint64_t i = 0; i < 2ull * n; ++i)
+        if (off[i + 1] < off[i])
+            return QHUFF_EINVAL;
+    const qhuff::HashMem r{in};
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const uint32_t a = off[2ull * i], m = off[2ull * i + 1],
+                       b = off[2ull * i + 2];
+        const uint32_t h1 = qhuff::xxh32(r, a, m - a, QHUFF_XXH_SEED);
+        const uint32_t h2 = qhuff::xxh32(r, m, b - m, h1);
+        const qhuff::StaticHit hit = qhuff::static_lookup(r, a, m, b, h1, h2,
+                                                          kStaticHost);
+        if (name_hash)
+            name_hash[i] = h1;
+        if (nameval_hash)
+            nameval_hash[i] = h2;
+        kind[i] = (uint8_t) hit.kind;
+        static_id[i] = (uint8_t) hit.id;
+    }
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_static_probe_tables(uint8_t name2id_plus_one[512],
+                          uint8_t nameval2id_plus_one[512])
+{
+    if (!name2id_plus_one || !nameval2id_plus_one)
+        return QHUFF_EINVAL;
+    static_assert(qhuff::kStaticSlots == 512, "the public table size");
+    memcpy(name2id_plus_one, kStaticHost.name2id, 512);
+    memcpy(nameval2id_plus_one, kStaticHost.nameval2id, 512);
+    return QHUFF_OK;
 }
 
 // ---- literal framing from a precomputed payload ---

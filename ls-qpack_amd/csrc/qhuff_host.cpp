@@ -396,6 +396,10 @@ qhuff_close(qhuff_ctx *c)
         (void) hipFree(c->scan_ws);
     if (c->scan_ev)
         (void) hipEventDestroy(c->scan_ev);
+    if (c->hdr_ws)
+        (void) hipFree(c->hdr_ws);
+    if (c->hdr_ev)
+        (void) hipEventDestroy(c->hdr_ev);
     if (c->tev)
     {
         for (unsigned i = 0; i < 2 * QHUFF_TIMING_SLOTS; ++i)
@@ -1187,6 +1191,153 @@ qhuff_encode_wire(qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
             return launch_encwire(a, items, grid, st, e0, e1);
         });
     });
+}
+
+// ---- headers against the static table (qhuff_lookup.hip) -------------------
+
+static LookupArgs
+lookup_args(const uint8_t *in, const uint32_t *off, uint32_t n,
+            uint32_t *h1, uint32_t *h2, uint8_t *kind, uint8_t *id)
+{
+    LookupArgs a = {};
+    a.in = in;
+    a.off = off;
+    a.h1 = h1;
+    a.h2 = h2;
+    a.kind = kind;
+    a.id = id;
+    a.n = n;
+    return a;
+}
+
+// (the grid is the hash kernel's resident one, from hash_occupancy: the
+// lookup kernel has the hash kernel's LDS frame and, today, its occupancy --
+// 79 VGPRs, three workgroups a CU.  Should it grow past that, it needs an
+// occupancy query of its own to stay resident; any grid is correct.)
+static int
+lookup_launch(qhuff_ctx *c, const LookupArgs &a, hipStream_t st)
+{
+    return timed(c, QHUFF_KIND_HASH, "launch_lookup",
+                 [&](hipEvent_t e0, hipEvent_t e1) {
+        return launch_lookup(a, c->hash_grid, st, e0, e1);
+    });
+}
+
+extern "C" int
+qhuff_static_lookup(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                    uint32_t n, uint32_t *name_hash, uint32_t *nameval_hash,
+                    uint8_t *kind, uint8_t *static_id, void *stream)
+{
+    if (!c || !off || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0)
+        return QHUFF_OK;
+    return lookup_launch(c, lookup_args(in, off, n, name_hash, nameval_hash,
+                                        kind, static_id),
+                         (hipStream_t) stream);
+}
+
+extern "C" uint64_t
+qhuff_encode_headers_bound(uint64_t in_bytes, uint32_t n, uint32_t m)
+{
+    // two items a header and two a section prefix; above 32 bits (which the
+    // calls reject) the count saturates, and so does the bound
+    const uint64_t items = 2ull * n + 2ull * m;
+    if (items > 0xffffffffull)
+        return ~0ull;
+    return qhuff_encode_wire_bound(in_bytes, (uint32_t) items);
+}
+
+static inline size_t
+hdr_up16(size_t x)
+{
+    return (x + 15) & ~(size_t) 15;
+}
+
+// the scratch for `items` items, and this call's launches on st ordered
+// behind those that went out on another stream (one scratch per context)
+static int
+hdr_prepare(qhuff_ctx *c, uint64_t items, hipStream_t st)
+{
+    if (!c->hdr_ev)
+        HIPCHK(c, hipEventCreateWithFlags(&c->hdr_ev, hipEventDisableTiming));
+    if (c->hdr_have && st != c->hdr_stream)
+    {
+        HIPCHK(c, hipEventRecord(c->hdr_ev, c->hdr_stream));
+        HIPCHK(c, hipStreamWaitEvent(st, c->hdr_ev, 0));
+    }
+    if (items > c->hdr_cap)
+    {
+        if (c->hdr_ws)
+        {
+            // (earlier calls may still use it)
+            if (c->hdr_have)
+                HIPCHK(c, hipStreamSynchronize(c->hdr_stream));
+            HIPCHK(c, hipFree(c->hdr_ws));
+            c->hdr_ws = nullptr;
+            c->hdr_cap = 0;
+        }
+        const uint64_t cap = items < 4096 ? 4096 : items;
+        HIPCHK(c, hipMalloc((void **) &c->hdr_ws,
+                            8 * cap + 2 * hdr_up16(4 * (cap + 1))));
+        c->hdr_cap = cap;
+    }
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_encode_headers(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                     uint32_t n, const uint8_t *hflags,
+                     const uint32_t *sec_hdr, uint32_t m, uint8_t *out,
+                     uint32_t *sec_out, uint8_t *kind, uint8_t *static_id,
+                     void *stream)
+{
+    if (!c || !off || !sec_hdr || !sec_out || (n && !in) || ((n || m) && !out))
+        return QHUFF_EINVAL;
+    const uint64_t items = 2ull * n + 2ull * m;
+    if (items > 0xffffffffull)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (items == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(sec_out, 0, 4, st));
+        return QHUFF_OK;
+    }
+    // (headers without a section: sec_hdr[0] = 0 != n, the caller's breach)
+    if (m == 0)
+        return QHUFF_EINVAL;
+    if (n == 0)
+    {
+        // (no header: the sections are their prefixes, the strings unread)
+        HIPCHK(c, launch_empty_sections(m, out, sec_out, st));
+        return QHUFF_OK;
+    }
+    if (const int r = hdr_prepare(c, items, st))
+        return r;
+    LookupArgs a = lookup_args(in, off, n, nullptr, nullptr, kind, static_id);
+    a.hflags = hflags;
+    a.sec_hdr = sec_hdr;
+    a.m = m;
+    a.items = (struct qhuff_item *) c->hdr_ws;
+    a.str_off = (uint32_t *) (c->hdr_ws + 8 * c->hdr_cap);
+    uint32_t *item_off = (uint32_t *) (c->hdr_ws + 8 * c->hdr_cap
+                                       + hdr_up16(4 * (c->hdr_cap + 1)));
+    int r = lookup_launch(c, a, st);
+    if (r)
+        return r;
+    // (a launch went out: later calls on another stream wait for it)
+    c->hdr_stream = st;
+    c->hdr_have = true;
+    r = qhuff_encode_wire(c, in, a.str_off, a.items, (uint32_t) items, out,
+                          item_off, st);
+    if (r)
+        return r;
+    HIPCHK(c, launch_secout(item_off, sec_hdr, m, n, sec_out, st));
+    return QHUFF_OK;
 }
 
 // ---- host helpers --------------------------------------------------------------

@@ -1220,6 +1220,128 @@ qhuff_xxh32_headers_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
     return QHUFF_OK;
 }
 
+// ---- headers against the static table, host buffers ----------------------------
+
+// (the checks the host forms make of a header list: n within the pairs
+// layout's range, offsets that do not decrease)
+static int
+headers_ok(const uint32_t *off, uint32_t n)
+{
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    for (uint64_t i = 0; i < 2ull * n; ++i)
+        if (off[i + 1] < off[i])
+            return QHUFF_EINVAL;
+    return QHUFF_OK;
+}
+
+// Stage layout: [name/value bytes | offsets (2n + 1) | name_hash |
+// nameval_hash | kind | static_id]; `in` is passed rebased by -off[0].
+extern "C" int
+qhuff_static_lookup_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                         uint32_t n, uint32_t *name_hash,
+                         uint32_t *nameval_hash, uint8_t *kind,
+                         uint8_t *static_id)
+{
+    if (!c || !off || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    if (const int rc = headers_ok(off, n))
+        return rc;
+    if (n == 0)
+        return QHUFF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
+    const size_t o_off = up16(bytes) + 16;
+    const size_t o_h1 = o_off + up16(4ull * (2ull * n + 1));
+    const size_t o_h2 = o_h1 + up16(4ull * n), o_k = o_h2 + up16(4ull * n);
+    const size_t o_id = o_k + up16(n), total = o_id + up16(n);
+    int rc = stage_up(c, total, {{in + a0, bytes, 0},
+                                 {off, 4ull * (2ull * n + 1), o_off}}, o_h1);
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t st = c->own_stream;
+    rc = qhuff_static_lookup(c, D - a0, (const uint32_t *) (D + o_off), n,
+                             (uint32_t *) (D + o_h1), (uint32_t *) (D + o_h2),
+                             D + o_k, D + o_id, st);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(H + o_h1, D + o_h1, total - o_h1,
+                             hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (name_hash)
+        memcpy(name_hash, H + o_h1, 4ull * n);
+    if (nameval_hash)
+        memcpy(nameval_hash, H + o_h2, 4ull * n);
+    memcpy(kind, H + o_k, n);
+    memcpy(static_id, H + o_id, n);
+    return QHUFF_OK;
+}
+
+// Header lists to field sections (qhuff_encode_headers): the bytes, their
+// offsets, the flags and the sections' bounds go up in one copy; the
+// launches; sec_out, kind and static_id come back, then exactly the
+// sec_out[m] bytes written.  The host loops over the offsets and the
+// sections' bounds only to check them.  Stage layout: [bytes | off | hflags |
+// sec_hdr | sec_out | kind | static_id | out]; `in` is passed rebased by
+// -off[0].
+extern "C" int
+qhuff_encode_headers_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                          uint32_t n, const uint8_t *hflags,
+                          const uint32_t *sec_hdr, uint32_t m, uint8_t *out,
+                          uint32_t *sec_out, uint8_t *kind, uint8_t *static_id)
+{
+    if (!c || !off || !sec_hdr || !sec_out || (n && !in) || ((n || m) && !out))
+        return QHUFF_EINVAL;
+    if (2ull * n + 2ull * m > 0xffffffffull)
+        return QHUFF_ERANGE;
+    if (sec_hdr[0] != 0 || sec_hdr[m] != n)
+        return QHUFF_EINVAL;
+    for (uint32_t s = 0; s < m; ++s)
+        if (sec_hdr[s + 1] < sec_hdr[s])
+            return QHUFF_EINVAL;
+    if (const int rc = headers_ok(off, n))
+        return rc;
+    if (m == 0)
+    {
+        sec_out[0] = 0;
+        return QHUFF_OK;
+    }
+    const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
+    const uint64_t bound = qhuff_encode_headers_bound(bytes, n, m);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t o_off = up16(bytes) + 16;
+    const size_t o_fl = o_off + up16(4ull * (2ull * n + 1));
+    const size_t o_sh = o_fl + up16(n);
+    const size_t o_so = o_sh + up16(4ull * (m + 1ull));
+    const size_t o_k = o_so + up16(4ull * (m + 1ull));
+    const size_t o_id = o_k + up16(n), o_out = o_id + up16(n);
+    int rc = stage_up(c, o_out + up16(bound),
+                      {{bytes ? in + a0 : nullptr, bytes, 0},
+                       {off, 4ull * (2ull * n + 1), o_off},
+                       {hflags, hflags ? (size_t) n : 0, o_fl},
+                       {sec_hdr, 4ull * (m + 1ull), o_sh}}, o_so);
+    if (rc)
+        return rc;
+    uint8_t *D = c->d_stage;
+    rc = qhuff_encode_headers(c, D - a0, (const uint32_t *) (D + o_off), n,
+                              hflags ? D + o_fl : nullptr,
+                              (const uint32_t *) (D + o_sh), m, D + o_out,
+                              (uint32_t *) (D + o_so), D + o_k, D + o_id,
+                              c->own_stream);
+    if (rc)
+        return rc;
+    if ((rc = stage_down(c, o_so, o_so, o_out, m, out, sec_out)))
+        return rc;
+    if (kind && n)
+        memcpy(kind, c->h_stage + o_k, n);
+    if (static_id && n)
+        memcpy(static_id, c->h_stage + o_id, n);
+    return QHUFF_OK;
+}
+
 // ---- per-string mirrors -----------------------------------------------------
 
 extern "C" int

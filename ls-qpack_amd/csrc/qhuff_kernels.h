@@ -101,6 +101,25 @@ struct HashArgs
     uint32_t pairs;
 };
 
+// headers looked up in the static table, and their field lines' items
+// (qhuff_lookup.hip): the hash kernel's pairs layout.  Every output may be
+// null.  Encode form (items != null): m sections between sec_hdr[0 .. m];
+// items and str_off hold 2n + 2m items / 2n + 2m + 1 offsets (the context's
+// scratch, items 16-byte and str_off 8-byte aligned).
+struct LookupArgs
+{
+    const uint8_t *in;
+    const uint32_t *off;         // 2n + 1 offsets
+    uint32_t *h1, *h2;           // name hash, name+value hash
+    uint8_t *kind, *id;          // QHUFF_LINE_*, static index
+    const uint8_t *hflags;       // or null: all 0
+    const uint32_t *sec_hdr;
+    ::qhuff_item *items;
+    uint32_t *str_off;
+    uint64_t n;
+    uint32_t m;
+};
+
 // ---- low-latency service (qhuff_service.hip, qhuff_svc_host.cpp) ----------
 //
 // One request slot per service wave, in pinned host memory mapped into the
@@ -234,6 +253,17 @@ int encwire_waves_per_block();
 hipError_t launch_hash(const HashArgs &a, uint32_t max_grid, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 hipError_t hash_occupancy(int *blocks_per_cu);
+// (a.n != 0)
+hipError_t launch_lookup(const LookupArgs &a, uint32_t max_grid,
+                         hipStream_t st, hipEvent_t ev0 = nullptr,
+                         hipEvent_t ev1 = nullptr);
+// m sections of no headers: out = m x "00 00", sec_out[s] = 2s, s in [0, m]
+hipError_t launch_empty_sections(uint32_t m, uint8_t *out, uint32_t *sec_out,
+                                 hipStream_t st);
+// sec_out[s] = item_off[2 * sec_hdr[s] + 2 * s], s in [0, m]
+hipError_t launch_secout(const uint32_t *item_off, const uint32_t *sec_hdr,
+                         uint32_t m, uint64_t n, uint32_t *sec_out,
+                         hipStream_t st);
 // off[0 .. n) += add (shard stitching, qhuff_*_batch_multi)
 hipError_t launch_rebase(uint32_t *off, uint64_t n, uint32_t add,
                          hipStream_t st);

@@ -51,6 +51,10 @@ EXPORTS = (
     "qhuff_encode_wire_host",
     "qhuff_scan_sections", "qhuff_scan_sections_host",
     "qhuff_decode_sections_host", "qhuff_scan_sections_cpu",
+    "qhuff_static_lookup", "qhuff_static_lookup_host",
+    "qhuff_static_lookup_cpu", "qhuff_static_probe_tables",
+    "qhuff_encode_headers_bound", "qhuff_encode_headers",
+    "qhuff_encode_headers_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -65,6 +69,9 @@ LIT_NAME, LIT_VALUE = 1, 2
 MAX_STRLEN = 65535                        # QHUFF_MAX_STRLEN (LSXPACK_MAX_STRLEN)
 
 XXH_SEED = 39378473                       # LSQPACK_XXH_SEED, lsqpack.c:623
+HDR_NEVER_INDEX = 1                       # QHUFF_HDR_NEVER_INDEX, hflags bit 0
+LINE_INDEXED, LINE_NAMEREF, LINE_LITERAL = 0, 1, 2    # QHUFF_LINE_*
+STATIC_NONE = 0xFF                        # QHUFF_STATIC_NONE
 
 
 class QhuffError(RuntimeError):
@@ -314,6 +321,27 @@ def lib():
         L.qhuff_scan_sections_cpu.restype = C.c_int
         L.qhuff_scan_sections_cpu.argtypes = [vp, u32p, C.c_uint32, C.c_uint,
                                               vp, C.c_uint32, u32p, i32p, u32p]
+        L.qhuff_static_lookup.restype = C.c_int
+        L.qhuff_static_lookup.argtypes = [vp, vp, u32p, C.c_uint32, u32p, u32p,
+                                          vp, vp, vp]
+        L.qhuff_static_lookup_host.restype = C.c_int
+        L.qhuff_static_lookup_host.argtypes = [vp, vp, u32p, C.c_uint32, u32p,
+                                               u32p, vp, vp]
+        L.qhuff_static_lookup_cpu.restype = C.c_int
+        L.qhuff_static_lookup_cpu.argtypes = [vp, u32p, C.c_uint32, u32p, u32p,
+                                              vp, vp]
+        L.qhuff_static_probe_tables.restype = C.c_int
+        L.qhuff_static_probe_tables.argtypes = [vp, vp]
+        L.qhuff_encode_headers_bound.restype = C.c_uint64
+        L.qhuff_encode_headers_bound.argtypes = [C.c_uint64, C.c_uint32,
+                                                 C.c_uint32]
+        L.qhuff_encode_headers.restype = C.c_int
+        L.qhuff_encode_headers.argtypes = [vp, vp, u32p, C.c_uint32, vp, u32p,
+                                           C.c_uint32, vp, u32p, vp, vp, vp]
+        L.qhuff_encode_headers_host.restype = C.c_int
+        L.qhuff_encode_headers_host.argtypes = [vp, vp, u32p, C.c_uint32, vp,
+                                                u32p, C.c_uint32, vp, u32p, vp,
+                                                vp]
         _lib = L
     return _lib
 
@@ -506,6 +534,40 @@ def items_check(items):
     rc = lib().qhuff_items_check(_np_ptr(a) if len(a) else None,
                                  len(a) // 8, C.byref(bad))
     return rc, (bad.value if rc != OK else None)
+
+
+def encode_headers_bound(in_bytes, n, m):
+    return int(lib().qhuff_encode_headers_bound(in_bytes, n, m))
+
+
+def static_probe_tables():
+    """qhuff_static_probe_tables -> (name2id_plus_one, nameval2id_plus_one),
+    uint8 [512] each: the probe tables the library builds from the static
+    table with its own XXH32."""
+    import numpy as np
+    a, b = np.zeros(512, dtype=np.uint8), np.zeros(512, dtype=np.uint8)
+    rc = lib().qhuff_static_probe_tables(_np_ptr(a), _np_ptr(b))
+    if rc != OK:
+        raise QhuffError("qhuff_static_probe_tables failed: %d" % rc)
+    return a, b
+
+
+def static_lookup_cpu(data, off):
+    """qhuff_static_lookup_cpu: the lookup kernel's source run on the host
+    over headers data[off[2i] : off[2i+1]] / data[off[2i+1] : off[2i+2]] ->
+    (name_hash, nameval_hash uint32 [n], kind, static_id uint8 [n])."""
+    import numpy as np
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint32)
+    n = (len(off) - 1) // 2
+    h1, h2 = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+    kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+    rc = lib().qhuff_static_lookup_cpu(
+        _np_ptr(data) if len(data) else _np_ptr(np.zeros(1, np.uint8)),
+        _np_ptr(off), n, _np_ptr(h1), _np_ptr(h2), _np_ptr(kind), _np_ptr(sid))
+    if rc != OK:
+        raise QhuffError("qhuff_static_lookup_cpu failed: %d" % rc)
+    return h1[:n], h2[:n], kind[:n], sid[:n]
 
 
 def dec_int(buf, prefix_bits):
@@ -909,6 +971,96 @@ class Codec:
                                      h.data_ptr(), self._stream(stream))
         self._check(rc, "qhuff_xxh32_batch")
         return h[:n]
+
+    # headers against the static table, header lists to field sections -------
+    def static_lookup_into(self, data, off, n, name_hash, nameval_hash, kind,
+                           static_id, stream=None):
+        """qhuff_static_lookup on device tensors; name_hash / nameval_hash
+        may be None"""
+        rc = lib().qhuff_static_lookup(
+            self._ctx, data.data_ptr(), off.data_ptr(), n,
+            name_hash.data_ptr() if name_hash is not None else None,
+            nameval_hash.data_ptr() if nameval_hash is not None else None,
+            kind.data_ptr(), static_id.data_ptr(), self._stream(stream))
+        self._check(rc, "qhuff_static_lookup")
+
+    def static_lookup(self, data, off, stream=None):
+        """off: int32 cuda tensor [2n+1] (name, value, name, value ...).
+        Returns (name_hash, nameval_hash int32 [n] (uint32 bits), kind,
+        static_id uint8 [n])."""
+        import torch
+        n = (off.numel() - 1) // 2
+        h1, h2 = (torch.empty(max(n, 1), dtype=torch.int32, device=data.device)
+                  for _ in range(2))
+        kind, sid = (torch.empty(max(n, 1), dtype=torch.uint8,
+                                 device=data.device) for _ in range(2))
+        self.static_lookup_into(data, off, n, h1, h2, kind, sid, stream)
+        return h1[:n], h2[:n], kind[:n], sid[:n]
+
+    def static_lookup_host(self, data, off):
+        """Host numpy buffers -> (name_hash, nameval_hash uint32 [n], kind,
+        static_id uint8 [n])."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = (len(off) - 1) // 2
+        h1, h2 = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+        rc = lib().qhuff_static_lookup_host(
+            self._ctx, _np_ptr(data), _np_ptr(off), n, _np_ptr(h1),
+            _np_ptr(h2), _np_ptr(kind), _np_ptr(sid))
+        self._check(rc, "qhuff_static_lookup_host")
+        return h1[:n], h2[:n], kind[:n], sid[:n]
+
+    def encode_headers_into(self, data, off, n, hflags, sec_hdr, m, out,
+                            sec_out, kind=None, static_id=None, stream=None):
+        """qhuff_encode_headers on device tensors; hflags, kind and static_id
+        may be None.  sec_hdr must be a valid section list (the caller's
+        duty)."""
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        rc = lib().qhuff_encode_headers(
+            self._ctx, data.data_ptr(), off.data_ptr(), n, opt(hflags),
+            sec_hdr.data_ptr(), m, out.data_ptr(), sec_out.data_ptr(),
+            opt(kind), opt(static_id), self._stream(stream))
+        self._check(rc, "qhuff_encode_headers")
+
+    def encode_headers(self, data, off, sec_hdr, hflags=None, stream=None):
+        """data: uint8 cuda tensor; off: int32 cuda tensor [2n+1]; sec_hdr:
+        int32 cuda tensor [m+1]; hflags: uint8 cuda tensor [n] or None.
+        Returns (out uint8 [bound], sec_out int32 [m+1], kind, static_id
+        uint8 [n])."""
+        import torch
+        n, m = (off.numel() - 1) // 2, sec_hdr.numel() - 1
+        out = torch.empty(encode_headers_bound(int(data.numel()), n, m),
+                          dtype=torch.uint8, device=data.device)
+        sec_out = torch.empty(m + 1, dtype=torch.int32, device=data.device)
+        kind, sid = (torch.empty(max(n, 1), dtype=torch.uint8,
+                                 device=data.device) for _ in range(2))
+        self.encode_headers_into(data, off, n, hflags, sec_hdr, m, out,
+                                 sec_out, kind, sid, stream)
+        return out, sec_out, kind[:n], sid[:n]
+
+    def encode_headers_host(self, data, off, sec_hdr, hflags=None):
+        """qhuff_encode_headers_host over host buffers -> (out uint8 ndarray
+        [sec_out[m]], sec_out uint32 [m+1], kind, static_id uint8 [n])."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        sec_hdr = np.ascontiguousarray(sec_hdr, dtype=np.uint32)
+        if hflags is not None:
+            hflags = np.ascontiguousarray(hflags, dtype=np.uint8)
+        n, m = (len(off) - 1) // 2, len(sec_hdr) - 1
+        out = np.zeros(encode_headers_bound(int(off[-1]) - int(off[0]), n, m),
+                       dtype=np.uint8)
+        sec_out = np.zeros(m + 1, dtype=np.uint32)
+        kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+        rc = lib().qhuff_encode_headers_host(
+            self._ctx, _np_ptr(data) if len(data) else None, _np_ptr(off), n,
+            _np_ptr(hflags) if hflags is not None and n else None,
+            _np_ptr(sec_hdr), m, _np_ptr(out), _np_ptr(sec_out),
+            _np_ptr(kind), _np_ptr(sid))
+        self._check(rc, "qhuff_encode_headers_host")
+        return out[:sec_out[-1]], sec_out, kind[:n], sid[:n]
 
     # host-memory batch calls (numpy) ----------------------------------------
     def encode_host(self, data, in_off, mode=ENC_PAYLOAD, out=None,
