@@ -835,6 +835,153 @@ int qhuff_encode_headers_host(qhuff_ctx *ctx, const uint8_t *in,
                               uint32_t m, uint8_t *out, uint32_t *sec_out,
                               uint8_t *kind, uint8_t *static_id);
 
+/* ---- field sections decoded to header lists against the static table ------
+ * qhuff_scan_sections and qhuff_decode_wire give a section's literals and
+ * nothing else: an indexed line has none, a name-reference line only its
+ * value, and which static entry a line named, or its N bit, is not reported.
+ * These calls are the inverse of qhuff_encode_headers: for a field section
+ * that does not use the dynamic table the reference's decoder is stateless
+ * per line (header_out_static_entry, lsqpack.c:3013-3057;
+ * header_out_begin_static_nameref, 3121-3159; header_out_begin_literal /
+ * _write_name / _write_value, 3211-3323; the dispatch of parse_header_data,
+ * 3567-3915), and the result is a header list in the layout
+ * qhuff_encode_headers and qhuff_xxh32_headers take: off[2n + 1], name then
+ * value, packed.  QHUFF_FEATURE_DECODE_HEADERS and the symbols announce it
+ * (the ABI version is unchanged).
+ *
+ * Descriptors: one struct qhuff_hstr per string, two per header -- strings 2i
+ * and 2i + 1 are the name and the value of header i.  A WIRE string is a
+ * literal as in struct qhuff_literal; a STATIC string is the name or the
+ * value of static entry static_id and occupies no wire bytes.  The
+ * descriptors follow qhuff_decode_wire's order rule: pos does not decrease
+ * and pos[i] + len[i] <= pos[i + 1].
+ *
+ * qhuff_scan_headers walks m field sections (buf, sec_off as
+ * qhuff_scan_sections) and gives
+ *   rc[m]           per section, decided in this order:
+ *                   1. what qhuff_scan_field_section returns for the section
+ *                      alone when that is not OK (QHUFF_ETRUNC / QHUFF_EPROTO,
+ *                      QHUFF_MAX_STRLEN included);
+ *                   2. QHUFF_ENOTSUP: the Required Insert Count is not 0, or a
+ *                      line is a dynamic form -- indexed with T = 0, name
+ *                      reference with T = 0, indexed post-base, post-base name
+ *                      reference: the section needs the dynamic table; give
+ *                      it to the reference's decoder;
+ *                   3. QHUFF_EPROTO: a static index >= 99 (lsqpack.c:3021,
+ *                      3130);
+ *                   4. QHUFF_OK.
+ *                   With a Required Insert Count of 0 the Delta Base and its
+ *                   sign are read and ignored (lsqpack.c:4024-4028).  A
+ *                   section of just its two prefix bytes is OK, no headers.
+ *   hdr_off[m + 1]  hdr_off[0] = 0; section s holds the headers
+ *                   [hdr_off[s], hdr_off[s + 1]); a section that is not OK
+ *                   has none; hdr_off[m] is the full count whatever max_hdrs
+ *                   is;
+ *   and, for the headers with an index below max_hdrs,
+ *   strs            their two descriptors (strs holds 2 * max_hdrs);
+ *   kind[n]         QHUFF_LINE_INDEXED / _NAMEREF / _LITERAL;
+ *   static_id[n]    the entry the line named, QHUFF_STATIC_NONE for LITERAL;
+ *   hflags[n]       bit 0 (QHUFF_HDR_NEVER_INDEX) = the line's N bit, 0 for
+ *                   indexed lines
+ *   -- the arrays of the same names in qhuff_encode_headers; each of the three
+ *   may be NULL.
+ * qhuff_scan_headers: device pointers, asynchronous on `stream`, three
+ * launches none of which waits for another workgroup, timed as
+ * QHUFF_KIND_SCAN, on the scan's scratch; QHUFF_EINVAL for a null pointer;
+ * the caller reads hdr_off[m].  qhuff_scan_headers_host: host pointers, one
+ * staged round trip; QHUFF_EINVAL also for decreasing offsets; QHUFF_ERANGE
+ * when hdr_off[m] > max_hdrs, hdr_off and rc valid and the first max_hdrs
+ * headers returned.  qhuff_scan_headers_cpu: the kernels' walker source on the
+ * host over host pointers, no context and no device call; returns as the
+ * host form.  Reads and writes as qhuff_scan_sections: the outputs named
+ * above and nothing else, for m = 0 only hdr_off[0].
+ *
+ * qhuff_decode_headers: n headers = 2n descriptors (device pointers,
+ * asynchronous, one launch timed as QHUFF_KIND_DECODE).  Writes
+ * out[0 .. off[2n]), off[0 .. 2n] and status[0 .. 2n), nothing else; for
+ * n = 0 only off[0].  A WIRE string decodes exactly as in qhuff_decode_wire
+ * (Huffman as qhuff_decode_batch, raw copied); a STATIC string is the entry's
+ * name or value from RFC 9204 Appendix A.  A rejected string has
+ * QHUFF_DEC_ERROR and 0 bytes; its header's other string keeps its bytes: a
+ * header is good iff both statuses are 0.  max_len != 0: a string longer
+ * than max_len is rejected, and a value whose length plus its name's -- the
+ * name is string 2i, whatever its source, when its status is OK -- passes
+ * max_len (header_out_grow_buf, lsqpack.c:3346-3351, as the wire call).
+ * `out` must hold qhuff_decode_headers_bound(wire_bytes, n) = 8 * wire_bytes
+ * / 5 + 76 * n + 16 bytes (76: the longest static name + value).  The form
+ * of the descriptors is THE CALLER'S DUTY, as for qhuff_decode_wire; the
+ * kernel masks what it reads -- static_id clamped into the table, source and
+ * kind to a bit, a STATIC string's len taken as 0 -- so descriptors outside
+ * the rule give unspecified bytes, at most 53 for a STATIC string, for their
+ * own string only and no access outside the blocks of the wire span.
+ * QHUFF_EINVAL for a null pointer, QHUFF_ERANGE for n above 2^31 - 1.  One
+ * string a lane, 32 headers a tile; a tile whose wire span passes 3 KB or
+ * whose output, static bytes included, passes 3008 bytes takes the lean
+ * kernels' out-of-line path.
+ *
+ * qhuff_decode_headers_host: the whole path, as qhuff_decode_sections_host is
+ * for literals -- the wire bytes go up once, the scan runs, the small results
+ * come back (n = hdr_off[m]), the decode launch runs on the descriptors where
+ * they are, and off[0 .. 2n], status[0 .. 2n), the optional byte arrays and
+ * exactly off[2n] bytes come back; name_hash / nameval_hash (each may be
+ * NULL): qhuff_xxh32_headers with QHUFF_XXH_SEED runs over (out, off) on the
+ * device, by definition what qhuff_xxh32_headers gives on the returned
+ * arrays (LSQPACK_DEC_OPT_HASH_NAME / _NAMEVAL).  `out` holds
+ * qhuff_decode_headers_bound(wire bytes, max_hdrs), off 2 * max_hdrs + 1,
+ * status 2 * max_hdrs, the per-header arrays max_hdrs entries.  QHUFF_ERANGE
+ * when n > max_hdrs: nothing is decoded, out / off / status and the hashes
+ * are not written, hdr_off and rc are valid.  No loop over headers or
+ * strings on the host. */
+#define QHUFF_FEATURE_DECODE_HEADERS 1
+#define QHUFF_ENOTSUP   (-95)   /* the section needs the dynamic table     */
+#define QHUFF_HSTR_WIRE   0
+#define QHUFF_HSTR_STATIC 1
+
+struct qhuff_hstr {          /* 16 bytes, 4-byte aligned */
+    uint32_t pos;        /* WIRE: payload offset in buf.  STATIC: offset of
+                            its line's first byte                           */
+    uint32_t len;        /* WIRE: payload bytes.          STATIC: 0         */
+    uint8_t  huffman;    /* WIRE: H bit.                  STATIC: 0         */
+    uint8_t  source;     /* QHUFF_HSTR_WIRE / QHUFF_HSTR_STATIC             */
+    uint8_t  kind;       /* QHUFF_LIT_NAME / QHUFF_LIT_VALUE                */
+    uint8_t  static_id;  /* STATIC: the entry whose name or value this is;
+                            WIRE: QHUFF_STATIC_NONE                         */
+    uint32_t instr;      /* offset of its line's first byte                 */
+};
+
+int qhuff_scan_headers(qhuff_ctx *ctx, const uint8_t *buf,
+                       const uint32_t *sec_off, uint32_t m,
+                       struct qhuff_hstr *strs, uint32_t max_hdrs,
+                       uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                       uint8_t *static_id, uint8_t *hflags, void *stream);
+
+int qhuff_scan_headers_host(qhuff_ctx *ctx, const uint8_t *buf,
+                            const uint32_t *sec_off, uint32_t m,
+                            struct qhuff_hstr *strs, uint32_t max_hdrs,
+                            uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                            uint8_t *static_id, uint8_t *hflags);
+
+int qhuff_scan_headers_cpu(const uint8_t *buf, const uint32_t *sec_off,
+                           uint32_t m, struct qhuff_hstr *strs,
+                           uint32_t max_hdrs, uint32_t *hdr_off, int32_t *rc,
+                           uint8_t *kind, uint8_t *static_id,
+                           uint8_t *hflags);
+
+uint64_t qhuff_decode_headers_bound(uint64_t wire_bytes, uint32_t n);
+
+int qhuff_decode_headers(qhuff_ctx *ctx, const uint8_t *buf,
+                         const struct qhuff_hstr *strs, uint32_t n,
+                         uint32_t max_len, uint8_t *out, uint32_t *off,
+                         uint8_t *status, void *stream);
+
+int qhuff_decode_headers_host(qhuff_ctx *ctx, const uint8_t *buf,
+                              const uint32_t *sec_off, uint32_t m,
+                              uint32_t max_len, uint32_t max_hdrs,
+                              uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                              uint8_t *static_id, uint8_t *hflags,
+                              uint8_t *out, uint32_t *off, uint8_t *status,
+                              uint32_t *name_hash, uint32_t *nameval_hash);
+
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman
  * payload was precomputed by a QHUFF_ENC_PAYLOAD batch (huff, huff_len =

@@ -356,6 +356,44 @@ qhuff_scan_sections_cpu(const uint8_t *buf, const uint32_t *sec_off,
     return lit_off[m] > max_lits ? QHUFF_ERANGE : QHUFF_OK;
 }
 
+// qhuff_scan_headers' two passes in plain C++, section by section: the
+// kernels' header-line walker over the same reader.
+extern "C" int
+qhuff_scan_headers_cpu(const uint8_t *buf, const uint32_t *sec_off, uint32_t m,
+                       struct qhuff_hstr *strs, uint32_t max_hdrs,
+                       uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                       uint8_t *static_id, uint8_t *hflags)
+{
+    if (!hdr_off || (m && (!buf || !sec_off || !rc)) || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    for (uint32_t i = 0; i < m; ++i)
+        if (sec_off[i + 1] < sec_off[i])
+            return QHUFF_EINVAL;
+    HostReader r{buf};
+    // the count pass
+    hdr_off[0] = 0;
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        qhuff::scan::HdrCountSink s{0};
+        rc[i] = qhuff::scan::walk_header_section(r, s, sec_off[i],
+                                                 sec_off[i + 1]);
+        hdr_off[i + 1] = hdr_off[i] + s.n;
+    }
+    // the write pass
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        const uint32_t first = hdr_off[i];
+        const uint32_t last = hdr_off[i + 1] < max_hdrs ? hdr_off[i + 1]
+                                                        : max_hdrs;
+        if (hdr_off[i + 1] == first || first >= last)
+            continue;
+        qhuff::scan::HdrWriteSink w{strs, kind, static_id, hflags, first, last};
+        (void) qhuff::scan::walk_header_section(r, w, sec_off[i],
+                                                sec_off[i + 1]);
+    }
+    return hdr_off[m] > max_hdrs ? QHUFF_ERANGE : QHUFF_OK;
+}
+
 // ---- the lookup kernel's source on the host (qhuff_lookup_impl.h) -----------
 //
 // qhuff_static_lookup in plain C++, header by header: the kernels' XXH32 and

@@ -793,8 +793,9 @@ qhuff_batch_hint(qhuff_ctx *c, int kind, int hint)
 // ---- the tile calls' launch frame ------------------------------------------
 //
 // qhuff_encode_batch, qhuff_decode_batch, qhuff_decode_stream,
-// qhuff_decode_wire and qhuff_encode_wire check their own arguments and then
-// go through tile_launch; what differs between them is the body.
+// qhuff_decode_wire, qhuff_encode_wire and qhuff_decode_headers check their
+// own arguments and then go through tile_launch; what differs between them
+// is the body.
 
 static EncArgs
 enc_args(const qhuff_ctx *c, const uint8_t *in, const uint32_t *in_off,
@@ -1139,6 +1140,96 @@ qhuff_scan_sections(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
             return r;
     }
     return QHUFF_OK;
+}
+
+// ---- header lists from field sections (qhuff_hdrscan.hip, qhuff_hdrdec.hip) -
+
+// The literal scan's frame over the header walker: its scratch, its stream
+// ordering, its top launch.
+extern "C" int
+qhuff_scan_headers(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+                   uint32_t m, struct qhuff_hstr *strs, uint32_t max_hdrs,
+                   uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                   uint8_t *static_id, uint8_t *hflags, void *stream)
+{
+    if (!c || !hdr_off || (m && (!buf || !sec_off || !rc))
+            || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(hdr_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    if (const int r = scan_prepare(c, m, st))
+        return r;
+    HdrScanArgs a;
+    a.buf = buf;
+    a.sec_off = sec_off;
+    a.strs = strs;
+    a.hdr_off = hdr_off;
+    a.rc = rc;
+    a.kind = kind;
+    a.static_id = static_id;
+    a.hflags = hflags;
+    a.cnt = c->scan_ws;
+    a.tot = c->scan_ws + c->scan_cap;
+    a.m = m;
+    a.max_hdrs = max_hdrs;
+    ScanArgs top = {};                   // (the top launch reads tot and m)
+    top.tot = a.tot;
+    top.m = m;
+    for (unsigned step = 0; step < 3; ++step)
+    {
+        const int r = timed(c, QHUFF_KIND_SCAN, "launch_hdrscan",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return step == 1 ? launch_scan(top, 1, st, e0, e1)
+                             : launch_hdrscan(a, step, st, e0, e1);
+        });
+        if (step || !r)
+        {
+            c->scan_stream = st;
+            c->scan_have = true;
+        }
+        if (r)
+            return r;
+    }
+    return QHUFF_OK;
+}
+
+extern "C" uint64_t
+qhuff_decode_headers_bound(uint64_t wire_bytes, uint32_t n)
+{
+    // the literals as qhuff_decode_bound; per header the longest static name
+    // + value (qhuff_hdrdec_impl.h asserts the 76)
+    return wire_bytes * 8 / 5 + 76ull * n + 16;
+}
+
+extern "C" int
+qhuff_decode_headers(qhuff_ctx *c, const uint8_t *buf,
+                     const struct qhuff_hstr *strs, uint32_t n,
+                     uint32_t max_len, uint8_t *out, uint32_t *off,
+                     uint8_t *status, void *stream)
+{
+    if (!c || !off || (n && (!buf || !strs || !out || !status)))
+        return QHUFF_EINVAL;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    // (one string a lane: 2n strings, a tile 32 whole headers)
+    return tile_launch(c, 2 * n, decode_tile_strings(),
+                       hdrdec_waves_per_block(), c->dec_grid, off, st,
+                       [&](const Coord &k, uint32_t grid) -> int {
+        WireArgs a;
+        a.d = dec_args(c, buf, (const uint32_t *) strs, out, off, status,
+                       2 * n, k);
+        a.max_len = max_len;
+        return timed(c, QHUFF_KIND_DECODE, "launch_hdrdec",
+                     [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_hdrdec(a, grid, st, e0, e1);
+        });
+    });
 }
 
 // ---- items encoded in one launch (qhuff_encwire.hip) -----------------------

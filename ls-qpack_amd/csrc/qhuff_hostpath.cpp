@@ -1135,6 +1135,187 @@ qhuff_decode_sections_host(qhuff_ctx *c, const uint8_t *buf,
     return QHUFF_OK;
 }
 
+// ---- header lists from field sections (qhuff_scan_headers) ------------------
+
+// The first half of both host forms, as scan_staged: the wire bytes and their
+// offsets up, the header scan on the context's stream, hdr_off and rc back.
+// Stage layout: [16 | wire bytes | 16 | sec_off | hdr_off | rc | strs | kind |
+// static_id | hflags], the last four sized for max_hdrs; `extra` more bytes
+// are kept behind them, from o->end.
+struct HdrStage
+{
+    size_t strs, kind, id, hf, end;
+};
+
+static int
+hdr_staged(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+           uint32_t m, uint32_t max_hdrs, uint32_t *hdr_off, int32_t *rc,
+           uint64_t extra, HdrStage *o)
+{
+    const uint64_t a0 = sec_off[0], bytes = (uint64_t) sec_off[m] - a0;
+    const size_t o_so = up16(16 + bytes) + 16;
+    const size_t o_ho = o_so + up16(4ull * (m + 1));
+    const size_t o_rc = o_ho + up16(4ull * (m + 1));
+    o->strs = o_rc + up16(4ull * m);
+    o->kind = o->strs + 32ull * max_hdrs;
+    o->id = o->kind + up16(max_hdrs);
+    o->hf = o->id + up16(max_hdrs);
+    o->end = o->hf + up16(max_hdrs);
+    int r = stage_up(c, o->end + extra,
+                     {{buf + a0, bytes, 16}, {sec_off, 4ull * (m + 1), o_so}},
+                     o_ho);
+    if (r)
+        return r;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    r = qhuff_scan_headers(c, D + 16 - a0, (const uint32_t *) (D + o_so), m,
+                           (struct qhuff_hstr *) (D + o->strs), max_hdrs,
+                           (uint32_t *) (D + o_ho), (int32_t *) (D + o_rc),
+                           D + o->kind, D + o->id, D + o->hf, c->own_stream);
+    if (r)
+        return r;
+    HIPCHK(c, hipMemcpyAsync(H + o_ho, D + o_ho, o->strs - o_ho,
+                             hipMemcpyDeviceToHost, c->own_stream));
+    HIPCHK(c, hipStreamSynchronize(c->own_stream));
+    memcpy(hdr_off, H + o_ho, 4ull * (m + 1));
+    memcpy(rc, H + o_rc, 4ull * m);
+    return QHUFF_OK;
+}
+
+static bool
+hdr_args_ok(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+            uint32_t m, uint32_t *hdr_off, int32_t *rc)
+{
+    if (!c || !hdr_off || (m && (!buf || !sec_off || !rc)))
+        return false;
+    for (uint32_t i = 0; i < m; ++i)
+        if (sec_off[i + 1] < sec_off[i])
+            return false;
+    return true;
+}
+
+// the first n headers' byte arrays from the stage, those the caller asked for
+static void
+hdr_bytes_out(const qhuff_ctx *c, const HdrStage &o, uint32_t n, uint8_t *kind,
+              uint8_t *static_id, uint8_t *hflags)
+{
+    if (kind)
+        memcpy(kind, c->h_stage + o.kind, n);
+    if (static_id)
+        memcpy(static_id, c->h_stage + o.id, n);
+    if (hflags)
+        memcpy(hflags, c->h_stage + o.hf, n);
+}
+
+extern "C" int
+qhuff_scan_headers_host(qhuff_ctx *c, const uint8_t *buf,
+                        const uint32_t *sec_off, uint32_t m,
+                        struct qhuff_hstr *strs, uint32_t max_hdrs,
+                        uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                        uint8_t *static_id, uint8_t *hflags)
+{
+    if (!hdr_args_ok(c, buf, sec_off, m, hdr_off, rc) || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    if (m == 0)
+    {
+        hdr_off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HdrStage o;
+    int r = hdr_staged(c, buf, sec_off, m, max_hdrs, hdr_off, rc, 0, &o);
+    if (r)
+        return r;
+    const uint32_t n = hdr_off[m] < max_hdrs ? hdr_off[m] : max_hdrs;
+    if (n)
+    {
+        uint8_t *H = c->h_stage, *D = c->d_stage;
+        HIPCHK(c, hipMemcpyAsync(H + o.strs, D + o.strs, 32ull * n,
+                                 hipMemcpyDeviceToHost, c->own_stream));
+        HIPCHK(c, hipMemcpyAsync(H + o.kind, D + o.kind, o.hf + n - o.kind,
+                                 hipMemcpyDeviceToHost, c->own_stream));
+        HIPCHK(c, hipStreamSynchronize(c->own_stream));
+        memcpy(strs, H + o.strs, 32ull * n);
+        hdr_bytes_out(c, o, n, kind, static_id, hflags);
+    }
+    return hdr_off[m] > max_hdrs ? QHUFF_ERANGE : QHUFF_OK;
+}
+
+// The whole path: hdr_staged, then qhuff_decode_headers on the descriptors
+// where the scan left them and, if asked for, qhuff_xxh32_headers over its
+// output where that lies; then the byte arrays, off, status and hashes in one
+// copy and exactly off[2n] bytes in another.  Behind the scan's regions the
+// stage holds [off | status | name_hash | nameval_hash | out], laid out for
+// the n headers there are.
+extern "C" int
+qhuff_decode_headers_host(qhuff_ctx *c, const uint8_t *buf,
+                          const uint32_t *sec_off, uint32_t m,
+                          uint32_t max_len, uint32_t max_hdrs,
+                          uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                          uint8_t *static_id, uint8_t *hflags, uint8_t *out,
+                          uint32_t *off, uint8_t *status, uint32_t *name_hash,
+                          uint32_t *nameval_hash)
+{
+    if (!off || !hdr_args_ok(c, buf, sec_off, m, hdr_off, rc)
+            || (max_hdrs && (!out || !status)))
+        return QHUFF_EINVAL;
+    if (max_hdrs > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    if (m == 0)
+    {
+        hdr_off[0] = 0;
+        off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t bytes = (uint64_t) sec_off[m] - sec_off[0];
+    if (qhuff_decode_headers_bound(bytes, max_hdrs) > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const uint64_t mh = max_hdrs;
+    HdrStage o;
+    int r = hdr_staged(c, buf, sec_off, m, max_hdrs, hdr_off, rc,
+                       up16(4 * (2 * mh + 1)) + up16(2 * mh)
+                           + 2 * up16(4 * mh)
+                           + up16(qhuff_decode_headers_bound(bytes, max_hdrs)),
+                       &o);
+    if (r)
+        return r;
+    const uint32_t n = hdr_off[m];
+    if (n > max_hdrs)
+        return QHUFF_ERANGE;
+    const size_t o_off = o.end;
+    const size_t o_st = o_off + up16(4 * (2ull * n + 1));
+    const size_t o_h1 = o_st + up16(2ull * n);
+    const size_t o_h2 = o_h1 + up16(4ull * n);
+    const size_t o_out = o_h2 + up16(4ull * n);
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    r = qhuff_decode_headers(c, D + 16 - sec_off[0],
+                             (const struct qhuff_hstr *) (D + o.strs), n,
+                             max_len, D + o_out, (uint32_t *) (D + o_off),
+                             D + o_st, c->own_stream);
+    if (r)
+        return r;
+    if (n && (name_hash || nameval_hash))
+    {
+        r = qhuff_xxh32_headers(c, D + o_out, (const uint32_t *) (D + o_off),
+                                n, QHUFF_XXH_SEED, (uint32_t *) (D + o_h1),
+                                (uint32_t *) (D + o_h2), c->own_stream);
+        if (r)
+            return r;
+    }
+    if ((r = stage_down(c, o.kind, o_off, o_out, 2 * n, out, off)))
+        return r;
+    if (n)
+    {
+        hdr_bytes_out(c, o, n, kind, static_id, hflags);
+        memcpy(status, H + o_st, 2ull * n);
+        if (name_hash)
+            memcpy(name_hash, H + o_h1, 4ull * n);
+        if (nameval_hash)
+            memcpy(nameval_hash, H + o_h2, 4ull * n);
+    }
+    return QHUFF_OK;
+}
+
 // Items encoded in one launch (qhuff_encode_wire): the strings, their
 // offsets and the items go up in one copy; one launch; the offsets come
 // back, then exactly the out_off[n] bytes written.  Nothing is framed or

@@ -90,6 +90,21 @@ struct ScanArgs
     uint32_t m, max_lits, mode;
 };
 
+// field sections walked for their header lines (qhuff_hdrscan.hip): the
+// scan's sections and scratch; strs holds 2 * max_hdrs descriptors; kind,
+// static_id and hflags may each be null
+struct HdrScanArgs
+{
+    const uint8_t *buf;
+    const uint32_t *sec_off;
+    ::qhuff_hstr *strs;
+    uint32_t *hdr_off;
+    int32_t *rc;
+    uint8_t *kind, *static_id, *hflags;
+    uint32_t *cnt, *tot;
+    uint32_t m, max_hdrs;
+};
+
 struct HashArgs
 {
     const uint8_t *in;
@@ -244,6 +259,15 @@ int wire_waves_per_block();
 // launch `step` of a scan's three (0 count, 1 top, 2 write), m >= 1
 hipError_t launch_scan(const ScanArgs &a, unsigned step, hipStream_t st,
                        hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// the count (step 0) and write (step 2) launches of a header scan, m >= 1;
+// its sums are launch_scan's step 1 over the same tot
+hipError_t launch_hdrscan(const HdrScanArgs &a, unsigned step, hipStream_t st,
+                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// header lists decoded from their descriptors (qhuff_hdrdec.hip): the wire
+// call's arguments, d.in_off the 2n descriptors (struct qhuff_hstr), d.n = 2n
+hipError_t launch_hdrdec(const WireArgs &a, uint32_t grid, hipStream_t st,
+                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int hdrdec_waves_per_block();
 // items encoded in one launch (qhuff_encwire.hip): the encode arguments
 // (mode unused: every item has its own framing) and the n items
 hipError_t launch_encwire(const EncArgs &a, const ::qhuff_item *items,

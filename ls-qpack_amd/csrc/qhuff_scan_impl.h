@@ -270,5 +270,190 @@ walk_chunk(R &r, S &s, unsigned mode, uint32_t a, uint32_t b,
     return QHUFF_OK;
 }
 
+// ---- header lines (qhuff_scan_headers) --------------------------------------
+//
+// The same sections walked for their header lines: what the reference's
+// decoder does per line when the dynamic table is not used
+// (header_out_static_entry, header_out_begin_static_nameref,
+// header_out_begin_literal: lsqpack.c:3013-3057, 3121-3159, 3211-3323).
+
+// a literal() sink that keeps the literal for the line it belongs to
+struct LitCatch
+{
+    Lit l;
+    QH_HD void put(const Lit &x, uint32_t) { l = x; }
+};
+
+QH_HD inline ::qhuff_hstr
+hstr_wire(const Lit &l, uint32_t kind, uint32_t at)
+{
+    ::qhuff_hstr d;
+    d.pos = l.pos;
+    d.len = l.len;
+    d.huffman = l.h;
+    d.source = QHUFF_HSTR_WIRE;
+    d.kind = (uint8_t) kind;
+    d.static_id = QHUFF_STATIC_NONE;
+    d.instr = at;
+    return d;
+}
+
+QH_HD inline ::qhuff_hstr
+hstr_static(uint32_t id, uint32_t kind, uint32_t at)
+{
+    ::qhuff_hstr d;
+    d.pos = at;
+    d.len = 0;
+    d.huffman = 0;
+    d.source = QHUFF_HSTR_STATIC;
+    d.kind = (uint8_t) kind;
+    d.static_id = (uint8_t) id;
+    d.instr = at;
+    return d;
+}
+
+// header sinks: line(kind, id, nbit, at, name, value) takes the next header
+// line -- kind QHUFF_LINE_*, id its static index (any for LITERAL), at its
+// first byte, name / value its literals where the kind has them
+struct HdrCountSink
+{
+    uint32_t n;
+    QH_HD void line(uint32_t, uint32_t, uint32_t, uint32_t, const Lit &,
+                    const Lit &)
+    {
+        ++n;
+    }
+};
+
+// headers with indices in [n0, limit) are written: two descriptors and a
+// byte of each array that is there
+struct HdrWriteSink
+{
+    ::qhuff_hstr *strs;
+    uint8_t *kind, *static_id, *hflags;
+    uint32_t n, limit;
+    QH_HD void line(uint32_t k, uint32_t id, uint32_t nbit, uint32_t at,
+                    const Lit &name, const Lit &value)
+    {
+        if (n < limit)
+        {
+            const uint64_t i = 2 * (uint64_t) n;
+            strs[i] = k == QHUFF_LINE_LITERAL
+                          ? hstr_wire(name, QHUFF_LIT_NAME, at)
+                          : hstr_static(id, QHUFF_LIT_NAME, at);
+            strs[i + 1] = k == QHUFF_LINE_INDEXED
+                              ? hstr_static(id, QHUFF_LIT_VALUE, at)
+                              : hstr_wire(value, QHUFF_LIT_VALUE, at);
+            if (kind)
+                kind[n] = (uint8_t) k;
+            if (static_id)
+                static_id[n] = (uint8_t) (k == QHUFF_LINE_LITERAL
+                                              ? QHUFF_STATIC_NONE : id);
+            if (hflags)
+                hflags[n] = (uint8_t) (nbit ? QHUFF_HDR_NEVER_INDEX : 0);
+        }
+        ++n;
+    }
+};
+
+constexpr uint32_t kHdrStaticEntries = 99;    // lsqpack.c:3021, 3130
+
+// One complete field section in [p, end) walked for its header lines: the
+// framing result of walk_field_section (0, -1 or -2) -- the walk goes on to
+// the section's end whatever the lines mean, so that a framing error wins --
+// and in *flags bit 0: the section needs the dynamic table (Required Insert
+// Count != 0 or a dynamic form), bit 1: a static index >= 99.  Lines are
+// reported until the first flag is raised.
+template <class R, class S>
+QH_HD inline int
+walk_header_lines(R &r, S &s, uint32_t p, uint32_t end, uint32_t *flags)
+{
+    const uint32_t max_str = QHUFF_MAX_STRLEN;
+    uint64_t ric, v;
+    int rc;
+    uint32_t f = 0;
+    *flags = 0;
+    // (the Delta Base and its sign are read and ignored)
+    if ((rc = dec_int(r, &p, end, 8, &ric)) || (rc = dec_int(r, &p, end, 7, &v)))
+        return rc;
+    if (ric)
+        f |= 1;
+    while (p < end)
+    {
+        const uint8_t b = r.get(p);
+        const uint32_t at = p;
+        uint32_t idx = 0, k = QHUFF_LINE_LITERAL, nbit = 0;
+        bool dyn = false;
+        LitCatch name, value;
+        name.l = Lit();
+        value.l = Lit();
+        if (b & 0x80)                          // 1Txxxxxx indexed field line
+        {
+            rc = dec_int24(r, &p, end, 6, &idx);
+            k = QHUFF_LINE_INDEXED;
+            dyn = !(b & 0x40);
+        }
+        else if (b & 0x40)                     // 01NTxxxx literal, name ref
+        {
+            rc = dec_int24(r, &p, end, 4, &idx);
+            if (!rc)
+                rc = literal(r, value, &p, end, 7, QHUFF_LIT_VALUE, at,
+                             max_str);
+            k = QHUFF_LINE_NAMEREF;
+            nbit = b & 0x20;
+            dyn = !(b & 0x10);
+        }
+        else if (b & 0x20)                     // 001NHxxx literal name
+        {
+            rc = literal(r, name, &p, end, 3, QHUFF_LIT_NAME, at, max_str);
+            if (!rc)
+                rc = literal(r, value, &p, end, 7, QHUFF_LIT_VALUE, at,
+                             max_str);
+            nbit = b & 0x10;
+        }
+        else if (b & 0x10)                     // 0001xxxx indexed post-base
+        {
+            rc = dec_int24(r, &p, end, 4, &idx);
+            dyn = true;
+        }
+        else                                   // 0000Nxxx post-base name ref
+        {
+            rc = dec_int24(r, &p, end, 3, &idx);
+            if (!rc)
+                rc = literal(r, value, &p, end, 7, QHUFF_LIT_VALUE, at,
+                             max_str);
+            dyn = true;
+        }
+        if (rc)
+            return rc;
+        if (dyn)
+            f |= 1;
+        else if (k != QHUFF_LINE_LITERAL && idx >= kHdrStaticEntries)
+            f |= 2;
+        if (!f)
+            s.line(k, idx, nbit, at, name.l, value.l);
+    }
+    *flags = f;
+    return 0;
+}
+
+// One section [a, b): its QHUFF_* result in the order of qhuff_scan_headers;
+// the sink's n has advanced by the section's headers, or is back where it
+// was when the result is not QHUFF_OK.
+template <class R, class S>
+QH_HD inline int
+walk_header_section(R &r, S &s, uint32_t a, uint32_t b)
+{
+    const uint32_t n0 = s.n;
+    uint32_t flags;
+    const int rc = walk_header_lines(r, s, a, b, &flags);
+    if (!rc && !flags)
+        return QHUFF_OK;
+    s.n = n0;
+    return rc == -1 ? QHUFF_ETRUNC
+         : rc ? QHUFF_EPROTO
+         : (flags & 1) ? QHUFF_ENOTSUP : QHUFF_EPROTO;
+}
+
 }  // namespace scan
 }  // namespace qhuff

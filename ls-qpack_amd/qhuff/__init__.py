@@ -55,12 +55,17 @@ EXPORTS = (
     "qhuff_static_lookup_cpu", "qhuff_static_probe_tables",
     "qhuff_encode_headers_bound", "qhuff_encode_headers",
     "qhuff_encode_headers_host",
+    "qhuff_scan_headers", "qhuff_scan_headers_host", "qhuff_scan_headers_cpu",
+    "qhuff_decode_headers_bound", "qhuff_decode_headers",
+    "qhuff_decode_headers_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
     "qhuff_lsqpack_set_context",
 )
 EPROTO, ETRUNC = -71, -61
+ENOTSUP = -95                             # QHUFF_ENOTSUP (qhuff_scan_headers)
+HSTR_WIRE, HSTR_STATIC = 0, 1             # QHUFF_HSTR_*
 TIMING_SLOTS = 256                        # QHUFF_TIMING_SLOTS
 KIND_ENCODE, KIND_DECODE, KIND_HASH = 0, 1, 2
 KIND_SCAN = 3                             # qhuff_scan_sections' three launches
@@ -83,6 +88,14 @@ class Literal(C.Structure):
     _fields_ = [("pos", C.c_uint32), ("len", C.c_uint32),
                 ("huffman", C.c_uint8), ("prefix_bits", C.c_uint8),
                 ("kind", C.c_uint8), ("hdr_len", C.c_uint8),
+                ("instr", C.c_uint32)]
+
+
+class Hstr(C.Structure):
+    """struct qhuff_hstr (include/qhuff.h): one string of a header"""
+    _fields_ = [("pos", C.c_uint32), ("len", C.c_uint32),
+                ("huffman", C.c_uint8), ("source", C.c_uint8),
+                ("kind", C.c_uint8), ("static_id", C.c_uint8),
                 ("instr", C.c_uint32)]
 
 
@@ -342,6 +355,27 @@ def lib():
         L.qhuff_encode_headers_host.argtypes = [vp, vp, u32p, C.c_uint32, vp,
                                                 u32p, C.c_uint32, vp, u32p, vp,
                                                 vp]
+        L.qhuff_scan_headers.restype = C.c_int
+        L.qhuff_scan_headers.argtypes = [vp, vp, vp, C.c_uint32, vp,
+                                         C.c_uint32, vp, vp, vp, vp, vp, vp]
+        L.qhuff_scan_headers_host.restype = C.c_int
+        L.qhuff_scan_headers_host.argtypes = [vp, vp, u32p, C.c_uint32, vp,
+                                              C.c_uint32, u32p, i32p, vp, vp,
+                                              vp]
+        L.qhuff_scan_headers_cpu.restype = C.c_int
+        L.qhuff_scan_headers_cpu.argtypes = [vp, u32p, C.c_uint32, vp,
+                                             C.c_uint32, u32p, i32p, vp, vp,
+                                             vp]
+        L.qhuff_decode_headers_bound.restype = C.c_uint64
+        L.qhuff_decode_headers_bound.argtypes = [C.c_uint64, C.c_uint32]
+        L.qhuff_decode_headers.restype = C.c_int
+        L.qhuff_decode_headers.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32,
+                                           vp, u32p, vp, vp]
+        L.qhuff_decode_headers_host.restype = C.c_int
+        L.qhuff_decode_headers_host.argtypes = [vp, vp, u32p, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, u32p,
+                                                i32p, vp, vp, vp, vp, u32p, vp,
+                                                u32p, u32p]
         _lib = L
     return _lib
 
@@ -477,6 +511,54 @@ def scan_sections_cpu(buf, sec_off, mode=SCAN_FIELD_SECTION, max_lits=None):
         raise QhuffError("qhuff_scan_sections_cpu failed: %d" % ret)
     n = min(int(lit_off[-1]), max_lits)
     return ret, lits[:16 * n], lit_off, rc[:m], consumed[:m]
+
+
+def decode_headers_bound(wire_bytes, n):
+    return int(lib().qhuff_decode_headers_bound(wire_bytes, n))
+
+
+def _headers_host_args(buf, sec_off, max_hdrs):
+    """the header scans' host arrays: (buf, sec_off, m, strs, hdr_off, rc,
+    kind, static_id, hflags)"""
+    import numpy as np
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    sec_off = np.ascontiguousarray(sec_off, dtype=np.uint32)
+    m = len(sec_off) - 1
+    k = max(max_hdrs, 1)
+    return (buf, sec_off, m, np.zeros(32 * k, dtype=np.uint8),
+            np.zeros(m + 1, dtype=np.uint32), np.zeros(max(m, 1), dtype=np.int32),
+            np.zeros(k, dtype=np.uint8), np.zeros(k, dtype=np.uint8),
+            np.zeros(k, dtype=np.uint8))
+
+
+def scan_headers_cpu(buf, sec_off, max_hdrs=None):
+    """qhuff_scan_headers_cpu: the header scan's walker run on the host over
+    sections buf[sec_off[i] : sec_off[i + 1]] -> (ret, strs, hdr_off, rc,
+    kind, static_id, hflags): ret OK or ERANGE (hdr_off[-1] > max_hdrs), strs
+    the uint8 array of the 2 * min(hdr_off[-1], max_hdrs) descriptors written
+    (16 bytes each).  max_hdrs None: a first call with room for none counts
+    them."""
+    if max_hdrs is None:
+        max_hdrs = int(scan_headers_cpu(buf, sec_off, 0)[2][-1])
+    buf, sec_off, m, strs, hdr_off, rc, kind, sid, hf = \
+        _headers_host_args(buf, sec_off, max_hdrs)
+    ret = lib().qhuff_scan_headers_cpu(
+        _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off), m,
+        _np_ptr(strs), max_hdrs, _np_ptr(hdr_off), _np_ptr(rc), _np_ptr(kind),
+        _np_ptr(sid), _np_ptr(hf))
+    if ret not in (OK, ERANGE):
+        raise QhuffError("qhuff_scan_headers_cpu failed: %d" % ret)
+    n = min(int(hdr_off[-1]), max_hdrs)
+    return ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n], hf[:n]
+
+
+def hstrs_array(strs):
+    """[Hstr] -> the descriptors as qhuff_decode_headers reads them: a numpy
+    uint8 array of 16 bytes each (two a header)."""
+    import numpy as np
+    n = len(strs)
+    arr = (Hstr * max(n, 1))(*strs)
+    return np.frombuffer(bytes(arr), dtype=np.uint8)[:16 * n].copy()
 
 
 def literals_array(lits):
@@ -1061,6 +1143,114 @@ class Codec:
             _np_ptr(kind), _np_ptr(sid))
         self._check(rc, "qhuff_encode_headers_host")
         return out[:sec_out[-1]], sec_out, kind[:n], sid[:n]
+
+    # field sections decoded to header lists --------------------------------
+    def scan_headers_into(self, buf, sec_off, m, strs, max_hdrs, hdr_off, rc,
+                          kind=None, static_id=None, hflags=None, stream=None):
+        """qhuff_scan_headers: all device tensors; strs holds 32 * max_hdrs
+        bytes; kind, static_id and hflags may be None."""
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        r = lib().qhuff_scan_headers(
+            self._ctx, buf.data_ptr(), sec_off.data_ptr(), m, opt(strs),
+            max_hdrs, hdr_off.data_ptr(), rc.data_ptr(), opt(kind),
+            opt(static_id), opt(hflags), self._stream(stream))
+        self._check(r, "qhuff_scan_headers")
+
+    def scan_headers(self, buf, sec_off, max_hdrs, stream=None):
+        """buf: uint8 cuda tensor of wire bytes; sec_off: int32 cuda tensor
+        [m+1].  Returns device tensors (strs uint8 [32 * max_hdrs], hdr_off
+        int32 [m+1], rc int32 [m], kind, static_id, hflags uint8 [max_hdrs]);
+        hdr_off[m] is the full count, to be compared with max_hdrs."""
+        import torch
+        m = sec_off.numel() - 1
+        dev = buf.device
+        k = max(max_hdrs, 1)
+        strs = torch.empty(32 * k, dtype=torch.uint8, device=dev)
+        hdr_off = torch.empty(m + 1, dtype=torch.int32, device=dev)
+        rc = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        kind, sid, hf = (torch.empty(k, dtype=torch.uint8, device=dev)
+                         for _ in range(3))
+        self.scan_headers_into(buf, sec_off, m, strs, max_hdrs, hdr_off, rc,
+                               kind, sid, hf, stream)
+        return strs, hdr_off, rc[:m], kind, sid, hf
+
+    def scan_headers_host(self, buf, sec_off, max_hdrs=None):
+        """qhuff_scan_headers_host over host arrays -> as scan_headers_cpu
+        (max_hdrs None: a first call with room for none counts them)."""
+        if max_hdrs is None:
+            max_hdrs = int(self.scan_headers_host(buf, sec_off, 0)[2][-1])
+        buf, sec_off, m, strs, hdr_off, rc, kind, sid, hf = \
+            _headers_host_args(buf, sec_off, max_hdrs)
+        ret = lib().qhuff_scan_headers_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, _np_ptr(strs), max_hdrs, _np_ptr(hdr_off), _np_ptr(rc),
+            _np_ptr(kind), _np_ptr(sid), _np_ptr(hf))
+        if ret != ERANGE:
+            self._check(ret, "qhuff_scan_headers_host")
+        n = min(int(hdr_off[-1]), max_hdrs)
+        return ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n], hf[:n]
+
+    def decode_headers_into(self, buf, strs, n, max_len, out, off, status,
+                            stream=None):
+        """qhuff_decode_headers: buf the wire bytes, strs the 2n descriptors
+        (16 bytes each), all device tensors; the descriptors' form is the
+        caller's duty."""
+        rc = lib().qhuff_decode_headers(
+            self._ctx, buf.data_ptr(), strs.data_ptr(), n, max_len or 0,
+            out.data_ptr(), off.data_ptr(), status.data_ptr(),
+            self._stream(stream))
+        self._check(rc, "qhuff_decode_headers")
+
+    def decode_headers(self, buf, strs, n, max_len=None, stream=None,
+                       wire_bytes=None):
+        """buf: uint8 cuda tensor of wire bytes; strs: uint8 cuda tensor of
+        the 2n descriptors.  Returns (out uint8 [bound], off int32 [2n+1],
+        status uint8 [2n]).  wire_bytes: the sections' bytes when they are
+        fewer than buf's (the bound)."""
+        import torch
+        if wire_bytes is None:
+            wire_bytes = int(buf.numel())
+        out = torch.empty(decode_headers_bound(wire_bytes, n),
+                          dtype=torch.uint8, device=buf.device)
+        off = torch.empty(2 * n + 1, dtype=torch.int32, device=buf.device)
+        status = torch.empty(max(2 * n, 1), dtype=torch.uint8,
+                             device=buf.device)
+        self.decode_headers_into(buf, strs, n, max_len, out, off, status,
+                                 stream)
+        return out, off, status[:2 * n]
+
+    def decode_headers_host(self, buf, sec_off, max_len=None, max_hdrs=None,
+                            hashes=False):
+        """qhuff_decode_headers_host: scan and decode in one call -> (ret,
+        hdr_off, rc, kind, static_id, hflags, out, off, status[, name_hash,
+        nameval_hash]); ret OK, or ERANGE (hdr_off[-1] > max_hdrs: nothing
+        decoded, the arrays after rc None).  max_hdrs None:
+        scan_headers_host counts the headers first."""
+        import numpy as np
+        if max_hdrs is None:
+            max_hdrs = int(self.scan_headers_host(buf, sec_off, 0)[2][-1])
+        buf, sec_off, m, _, hdr_off, rc, kind, sid, hf = \
+            _headers_host_args(buf, sec_off, max_hdrs)
+        wire = max(int(sec_off[-1]) - int(sec_off[0]), 0)
+        out = np.zeros(decode_headers_bound(wire, max_hdrs), dtype=np.uint8)
+        off = np.zeros(2 * max_hdrs + 1, dtype=np.uint32)
+        status = np.zeros(max(2 * max_hdrs, 1), dtype=np.uint8)
+        h1, h2 = (np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+                  for _ in range(2))
+        ret = lib().qhuff_decode_headers_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, max_len or 0, max_hdrs, _np_ptr(hdr_off), _np_ptr(rc),
+            _np_ptr(kind), _np_ptr(sid), _np_ptr(hf), _np_ptr(out),
+            _np_ptr(off), _np_ptr(status), _np_ptr(h1) if hashes else None,
+            _np_ptr(h2) if hashes else None)
+        tail = (None,) * (8 if hashes else 6)
+        if ret == ERANGE:
+            return (ret, hdr_off, rc[:m]) + tail
+        self._check(ret, "qhuff_decode_headers_host")
+        n = int(hdr_off[-1])
+        res = (ret, hdr_off, rc[:m], kind[:n], sid[:n], hf[:n],
+               out[:off[2 * n]], off[:2 * n + 1], status[:2 * n])
+        return res + ((h1[:n], h2[:n]) if hashes else ())
 
     # host-memory batch calls (numpy) ----------------------------------------
     def encode_host(self, data, in_off, mode=ENC_PAYLOAD, out=None,
