@@ -202,13 +202,20 @@ def test_cpu_scan_cases(name):
         assert set(d.rc.tolist()) >= {0, qhuff.ETRUNC, qhuff.EPROTO, D.ENOTSUP}
 
 
+def every_static_id_sections():
+    """every id as an indexed line and as a name reference: a section an id,
+    then all the indexed lines in one section and all the name references in
+    another"""
+    secs = [sec(indexed(i), nameref(i, b"v%d" % i, 0, i & 1))
+            for i in range(99)]
+    return secs + [sec(*[indexed(i) for i in range(99)]),
+                   sec(*[nameref(i, b"") for i in range(99)])]
+
+
 def test_cpu_every_static_id():
     """every id as an indexed line and as a name reference, and the ids on
     each side of the prefix integers' boundaries"""
-    secs = [sec(indexed(i), nameref(i, b"v%d" % i, 0, i & 1))
-            for i in range(99)]
-    d = D.Decoded(secs + [sec(*[indexed(i) for i in range(99)]),
-                          sec(*[nameref(i, b"") for i in range(99)])])
+    d = D.Decoded(every_static_id_sections())
     assert not d.rc.any() and d.n == 4 * 99
     assert d.static_id[:8].tolist() == [0, 0, 1, 1, 2, 2, 3, 3]
     cpu(d)
@@ -223,13 +230,19 @@ def test_cpu_every_static_id():
     cpu(hs)
 
 
-def test_cpu_bad_static_ids():
-    """ids 99, 100 and 2^24 - 1 are QHUFF_EPROTO, 2^24 the integer's own"""
+def bad_static_id_sections():
+    """ids 98, 99, 100, 2^24 - 1 and 2^24: indexed, as a name reference, and
+    between two good lines"""
     secs = []
     for i in (98, 99, 100, (1 << 24) - 1, 1 << 24):
         secs += [sec(indexed(i)), sec(nameref(i, b"x")),
                  sec(indexed(1), nameref(i, b"x"), indexed(2))]
-    d = D.Decoded(secs)
+    return secs
+
+
+def test_cpu_bad_static_ids():
+    """ids 99, 100 and 2^24 - 1 are QHUFF_EPROTO, 2^24 the integer's own"""
+    d = D.Decoded(bad_static_id_sections())
     assert d.rc.tolist() == [0] * 3 + [qhuff.EPROTO] * 12
     assert d.n == 5
     cpu(d)
@@ -243,30 +256,36 @@ DYNAMIC = {
 }
 
 
-def test_cpu_dynamic_forms():
+def dynamic_form_sections():
+    """each dynamic form alone, between two good lines and behind one; then
+    RIC != 0 with static-only lines, and a Delta Base with its sign set
+    under RIC = 0 (read and ignored)"""
     secs = []
     for form in DYNAMIC.values():
         secs += [b"\0\0" + form, sec(indexed(1), form, indexed(2)),
                  sec(literal(b"n", b"v"), form)]
-    # RIC != 0 with static-only lines, and a Delta Base with its sign set
-    # under RIC = 0 (read and ignored)
-    secs += [b"\x01\x00" + indexed(17), b"\x05\x83" + nameref(1, b"/x"),
-             b"\x00\x80" + indexed(17), b"\x00\xff\x05" + indexed(17)]
-    d = D.Decoded(secs)
+    return secs + [b"\x01\x00" + indexed(17), b"\x05\x83" + nameref(1, b"/x"),
+                   b"\x00\x80" + indexed(17), b"\x00\xff\x05" + indexed(17)]
+
+
+def test_cpu_dynamic_forms():
+    d = D.Decoded(dynamic_form_sections())
     assert d.rc.tolist() == [D.ENOTSUP] * 14 + [0, 0]
     assert d.headers == [D.STATIC[17]] * 2
     cpu(d)
 
 
-def test_cpu_rc_order():
-    """one section for each pair of the order's clauses: the earlier wins
-    wherever in the section each cause lies"""
-    trunc = nameref(1, b"abc")[:-1]              # ends inside the value
-    proto = b"\xff" + b"\xff" * 10 + b"\x7f"     # an integer past 64 bits
+TRUNC = nameref(1, b"abc")[:-1]                  # ends inside the value
+PROTO = b"\xff" + b"\xff" * 10 + b"\x7f"         # an integer past 64 bits
+
+
+def rc_order_cases():
+    """[(section, its rc)]: one section for each pair of the order's clauses"""
+    trunc, proto = TRUNC, PROTO
     notsup = DYNAMIC["indexed_t0"]
     bad = indexed(99)
     E = qhuff
-    cases = [
+    return [
         (sec(notsup, trunc), E.ETRUNC), (sec(bad, trunc), E.ETRUNC),
         (sec(notsup, proto), E.EPROTO), (sec(bad, proto), E.EPROTO),
         (b"\x01\x00" + trunc, E.ETRUNC), (b"\x01\x00" + proto, E.EPROTO),
@@ -278,6 +297,12 @@ def test_cpu_rc_order():
         (sec(notsup, b"\x51" + Q.enc_int(0, 65536, 7)), E.EPROTO),
         (b"\0", E.ETRUNC), (b"", E.ETRUNC), (b"\0\0", E.OK),
     ]
+
+
+def test_cpu_rc_order():
+    """one section for each pair of the order's clauses: the earlier wins
+    wherever in the section each cause lies"""
+    cases = rc_order_cases()
     d = D.Decoded([c for c, _ in cases])
     assert d.rc.tolist() == [r for _, r in cases]
     cpu(d)
@@ -432,7 +457,10 @@ def check_decode(d, got):
     assert bytes(out) == d.data
 
 
-def check_host(codec, sections, max_len=MAXS):
+def check_host(codec, sections, max_len=MAXS, also=()):
+    """qhuff_decode_headers_host with hashes, and qhuff_scan_headers_host,
+    against the model; the reference's hashes of the first and the last
+    headers and of those with an index in `also`"""
     d = D.Decoded(sections, max_len)
     wire = np.frombuffer(d.wire, dtype=np.uint8)
     ret, hdr_off, rc, kind, sid, hf, out, off, st, h1, h2 = \
@@ -447,8 +475,10 @@ def check_host(codec, sections, max_len=MAXS):
     g1, g2 = codec.xxh32_headers_host(np.concatenate([out, np.zeros(16, np.uint8)]),
                                       off)
     assert np.array_equal(h1, g1) and np.array_equal(h2, g2)
-    for i in list(range(min(d.n, 40))) + list(range(max(d.n - 8, 0), d.n)):
-        assert (int(h1[i]), int(h2[i])) == M.hashes(*d.headers[i]), i
+    hd = d.headers
+    for i in sorted(set(range(min(d.n, 40))) | set(range(max(d.n - 8, 0), d.n))
+                    | set(also)):
+        assert (int(h1[i]), int(h2[i])) == M.hashes(*hd[i]), i
     # and the scan's host form
     check_scan(d, codec.scan_headers_host(wire, d.sec_off, d.n))
     return d
