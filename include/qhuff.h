@@ -1077,7 +1077,12 @@ int qhuff_timing_read(qhuff_ctx *ctx, uint32_t *kind, double *us, uint32_t max);
  * of earlier launches.)  Returns 1 if the context's last launch of `kind`
  * (QHUFF_KIND_ENCODE / QHUFF_KIND_DECODE) ran the full kernel, 0 if the
  * lean one or none yet, QHUFF_EINVAL otherwise.  Diagnostic: the output
- * bytes are the same either way. */
+ * bytes are the same either way.
+ * QHUFF_LB_REPLICA, read at qhuff_open like QHUFF_KERNELS, is a test and A/B
+ * knob of the tile kernels' look-back: the super-tile flags are kept in
+ * several replicas, and by default (unset, -1 or out of range) a wave polls
+ * the replica of its workgroup; r pins every wave's polls to replica r.
+ * The output bytes are the same either way. */
 int qhuff_kernel_variant(qhuff_ctx *ctx, int kind);
 
 /* Diagnostic: the most waves one launch of `kind` (QHUFF_KIND_ENCODE /

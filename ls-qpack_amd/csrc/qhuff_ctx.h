@@ -46,8 +46,8 @@ struct qhuff_ctx
     LongParams lp;
     unsigned long long *flags;           // device look-back workspace:
                                          // tile flags [cap_tiles], super
-                                         // flags [cap_super], super
-                                         // accumulators [2][cap_super]
+                                         // flags [kLbReplicas][cap_super],
+                                         // super accumulators [2][cap_super]
     uint32_t *err;                       // device: [0] error word, [1..3]
                                          // census, then claim counters
     uint64_t cap_tiles, cap_super;
@@ -68,6 +68,8 @@ struct qhuff_ctx
                                          // (host_hint), or -1: full
     int kernels;                         // QHUFF_KERNELS: 0 auto, 1 lean,
                                          // 2 full
+    int lb_replica;                      // QHUFF_LB_REPLICA: the super-flag
+                                         // replica every wave polls, or -1
     unsigned long long *prof;            // QHUFF_PROFILE builds: stamp buffer;
                                          // QH_PATH_TRACE builds: tile records
     size_t prof_words;                   // words of the last launch

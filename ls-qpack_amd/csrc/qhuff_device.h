@@ -60,6 +60,24 @@ constexpr uint32_t kAccStride = 32;
 // tile flags kFlagStride u64 apart (1: dense, a poll window is 4 lines;
 // 4 and 16 were equal / 3 % slower, profiles/r02_h/ab_tile_flag_stride.txt)
 constexpr uint32_t kFlagStride = 1;
+// Super-tile flags are kept in kLbReplicas copies, each on cache lines of
+// its own (sflag_stride() apart, a multiple of 256 B).  A publish writes
+// every copy with one atomic instruction (lane r on copy r); a wave polls
+// one copy, chosen from its workgroup index, so the ~3,000 waves that
+// re-poll an invalid super flag in the drain queue on kLbReplicas lines,
+// not on one, in front of the last tiles' own publishes and polls
+// ("Replicated super flags")
+#ifndef QH_LB_REPLICAS
+#define QH_LB_REPLICAS 8
+#endif
+constexpr uint32_t kLbReplicas = QH_LB_REPLICAS;
+static_assert(kLbReplicas >= 1 && kLbReplicas <= 64, "one lane a replica");
+// u64 words between two replicas: cap_super entries, up to whole 256 bytes
+__host__ __device__ __forceinline__ uint32_t
+sflag_stride(uint32_t cap_super)
+{
+    return (cap_super + 31u) & ~31u;
+}
 
 // error bits reported through Coord::err
 constexpr uint32_t kErrSpin = 1;            // look-back spin limit hit
@@ -83,6 +101,7 @@ struct Coord
                                             // QH_PATH_TRACE: tile records
     unsigned long long *flags;              // per-tile look-back flags
     unsigned long long *sflags;             // per-super-tile flags
+                                            // [kLbReplicas][sflag_stride()]
     unsigned long long *sacc;               // super accumulators [2][cap_super],
                                             // kAccStride apart
     uint32_t *tick;                         // tile tickets [2][kTickGroups],
@@ -91,7 +110,11 @@ struct Coord
     uint32_t *err_host;                     // its pinned host mirror
     uint32_t epoch;                         // launch tag carried in flags
     uint32_t n_tiles;
-    uint32_t cap_super;                     // sacc entries per parity
+    uint32_t cap_super : 24;                // sacc entries per parity (a
+                                            // launch has below 2^26 tiles)
+    uint32_t pin : 8;                       // 1 + the sflags replica every
+                                            // wave polls (QHUFF_LB_REPLICA),
+                                            // or 0: chosen by workgroup
     uint32_t spread;                        // > 0: the first `spread` waves of
                                             // each workgroup take one tile
                                             // each from counter 0 (batches
@@ -590,6 +613,21 @@ struct LookBack
     {
         return (uint64_t) c.epoch << 42;
     }
+    // word index of super flag j in the replica this wave polls (the
+    // replica is wave-uniform: the workgroup index follows the XCD, so the
+    // pollers of one L2 spread over all replicas).  32 bits: a launch has
+    // below 2^26 tiles, so the index stays below 2^27
+    __device__ __forceinline__ static uint32_t my_sflag(const Coord &c, uint32_t j)
+    {
+        // (the opaque copy has the three scalar instructions of the offset
+        // rebuilt at each poll: kept across the tile loop it cost the full
+        // decode kernel, at its 168 VGPRs, a spilled register reloaded in
+        // every iteration)
+        uint32_t b = blockIdx.x;
+        asm volatile("" : "+s"(b));
+        const uint32_t r = c.pin ? c.pin - 1u : b % kLbReplicas;
+        return r * sflag_stride(c.cap_super) + j;
+    }
     __device__ __forceinline__ uint64_t poll_tile(const Coord &c) const
     {
         const uint32_t lane = lane_id();
@@ -606,8 +644,8 @@ struct LookBack
                                                    uint32_t back) const
     {
         const int64_t j = (int64_t) s - 1 - lane_id() - 64 * (int64_t) back;
-        return __hip_atomic_load(&c.sflags[j < 0 ? 0 : j], __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
+        return __hip_atomic_load(&c.sflags[my_sflag(c, j < 0 ? 0u : (uint32_t) j)],
+                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // a polled super flag; before super 0: inclusive 0
     __device__ __forceinline__ uint64_t super_val(const Coord &c, uint32_t back,
@@ -644,8 +682,11 @@ struct LookBack
     __device__ __forceinline__ void publish_super(const Coord &c, uint64_t state,
                                                   uint64_t v) const
     {
-        if (lane_id() == 0)
-            __hip_atomic_fetch_max(&c.sflags[s], state | ep(c) | (v & kValMask),
+        // one instruction: lane r writes replica r
+        const uint32_t lane = lane_id();
+        if (lane < kLbReplicas)
+            __hip_atomic_fetch_max(&c.sflags[lane * sflag_stride(c.cap_super) + s],
+                                   state | ep(c) | (v & kValMask),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // the add that completed the super tile publishes its aggregate
@@ -752,11 +793,13 @@ struct LookBack
             if (!v)                                  // (as above)
                 fs = poll_super(c, back);
         }
-        // Every poll has been consumed, so nothing is outstanding here but
-        // the compiler cannot see that the re-poll loads (whose registers the
-        // flush reuses) have landed: without this wait it puts a vmcnt(0)
-        // into each partial-chunk store path of the flush, where it drains
-        // the tile's own dwordx4 stores issued just before (~2k cycles).
+        // Every poll has been consumed; what is still outstanding here is
+        // the next tile's offsets load, issued just before the flush, and
+        // this wait takes it too.  It stands here because the compiler
+        // cannot see that the re-poll loads (whose registers the flush
+        // reuses) have landed: without it, it puts a vmcnt(0) into each
+        // partial-chunk store path of the flush, where it drains the tile's
+        // own dwordx4 stores issued just before (~2k cycles).
         __builtin_amdgcn_s_waitcnt(0x0f70);
         if (lane == 0)
             __hip_atomic_store(&c.flags[(uint64_t) tile * kFlagStride],

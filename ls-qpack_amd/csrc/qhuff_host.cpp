@@ -302,6 +302,11 @@ qhuff_open(int device, qhuff_ctx **ctx_out)
     {
         const char *kv = getenv("QHUFF_KERNELS");
         c->kernels = !kv ? 0 : !strcmp(kv, "lean") ? 1 : !strcmp(kv, "full") ? 2 : 0;
+        // test / A-B knob: the super-flag replica every wave polls; unset,
+        // -1 or out of range: by workgroup (qhuff_device.h kLbReplicas)
+        const char *rv = getenv("QHUFF_LB_REPLICA");
+        const long r = rv ? strtol(rv, nullptr, 0) : -1;
+        c->lb_replica = r >= 0 && r < (long) kLbReplicas ? (int) r : -1;
     }
     if (e == hipSuccess)
         e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
@@ -473,13 +478,22 @@ qhuff_decode_bound(uint64_t in_bytes, uint32_t n)
 }
 
 // look-back workspace: the tile tickets [2][kTickGroups] (u32, kTickStride
-// apart), tile flags [cap_tiles], super flags [cap_super], super
-// accumulators [2][cap_super] (u64, kAccStride apart)
+// apart), tile flags [cap_tiles], super flags [kLbReplicas][cap_super] (each
+// replica from a 256-byte boundary), super accumulators [2][cap_super]
+// (u64, kAccStride apart)
 constexpr size_t kTickBytes = 4 * 2 * kTickGroups * kTickStride;
+static_assert(kTickBytes % 256 == 0, "the flags start on a 256-byte boundary");
+static uint64_t
+round_256b(uint64_t words)               // u64 words, up to whole 256 bytes
+{
+    return (words + 31) & ~(uint64_t) 31;
+}
 static size_t
 lb_bytes(uint64_t cap_tiles, uint64_t cap_super)
 {
-    return kTickBytes + 8 * (cap_tiles * kFlagStride + cap_super + 2 * cap_super * kAccStride);
+    return kTickBytes + 8 * (round_256b(cap_tiles * kFlagStride)
+                             + (uint64_t) kLbReplicas * sflag_stride((uint32_t) cap_super)
+                             + 2 * cap_super * kAccStride);
 }
 
 // make room for the look-back workspace of `tiles` tiles and advance the
@@ -584,9 +598,10 @@ coord(qhuff_ctx *c, uint64_t tiles, hipStream_t st)
 #endif
     k.tick = (uint32_t *) c->flags;
     k.flags = c->flags + kTickBytes / 8;
-    k.sflags = k.flags + c->cap_tiles * kFlagStride;
-    k.sacc = k.sflags + c->cap_super;
-    k.cap_super = (uint32_t) c->cap_super;
+    k.sflags = k.flags + round_256b(c->cap_tiles * kFlagStride);
+    k.sacc = k.sflags + (uint64_t) kLbReplicas * sflag_stride((uint32_t) c->cap_super);
+    k.cap_super = (uint32_t) c->cap_super;   // (below 2^20: n is 32 bits)
+    k.pin = (uint32_t) (c->lb_replica + 1);
     k.err = c->err;
     k.err_host = c->err_host_dev;
     k.epoch = c->epoch;
