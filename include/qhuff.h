@@ -982,6 +982,158 @@ int qhuff_decode_headers_host(qhuff_ctx *ctx, const uint8_t *buf,
                               uint8_t *out, uint32_t *off, uint8_t *status,
                               uint32_t *name_hash, uint32_t *nameval_hash);
 
+/* ---- header lists from field sections that use the dynamic table -----------
+ * The calls above, for sections that name dynamic entries, the table's
+ * entries given by the caller as plain arrays.  Decoding a section against
+ * the dynamic table is a read of that table: the reference's decoder resolves
+ * each dynamic line to an entry (qdec_get_table_entry_abs, lsqpack.c:
+ * 2768-2775) and copies name and value out (header_out_dynamic_entry,
+ * 3060-3117; header_out_begin_dynamic_nameref, from 3655-3662); inserts come
+ * only from the encoder stream (4544 ff.), which stays with the host.  With
+ * the entries at hand a dynamic line is per line and stateless, as a static
+ * one is.  QHUFF_FEATURE_DECODE_HEADERS_DYN and the symbols announce it (the
+ * ABI version is unchanged); the calls above behave as before.
+ *
+ * struct qhuff_dyn_table is a read-only view: the entries held decoded (plain
+ * bytes), oldest first, packed as a header list -- bytes, off[2d + 1] as
+ * qhuff_xxh32_headers' off -- entry k with the absolute index (0-based insert
+ * ordinal) first + k.  d = 0 with null pointers is legal.  max_entries is
+ * MaxEntries = max table capacity / 32 (lsqpack.c:2789).
+ *
+ * qhuff_scan_headers_dyn / _host / _cpu: the arguments of the
+ * qhuff_scan_headers family and
+ *   tab       the table;
+ *   sec_win   2m entries, or NULL: sec_win[2s] = the oldest absolute index
+ *             still live when section s is decoded, sec_win[2s + 1] = the
+ *             insert count it sees; the rule: first <= sec_win[2s] <=
+ *             sec_win[2s + 1] <= first + d.  NULL: every section sees
+ *             [first, first + d).  One batch may so hold sections decoded at
+ *             different moments against one history of entries;
+ *   dyn_id    n entries, or NULL: the absolute index a line named, or
+ *             QHUFF_DYN_NONE.
+ * rc[s] is decided in this order (ins = the section's insert count):
+ *   1. what qhuff_scan_field_section returns for the section alone when that
+ *      is not OK;
+ *   2. QHUFF_EPROTO: the encoded Required Insert Count is above 2 *
+ *      max_entries (lsqpack.c:3973) -- any non-zero one when max_entries = 0;
+ *   3. the Required Insert Count (RFC 9204 4.5.1.1; the reference's modular
+ *      ids, ID_MINUS, qdec_in_future, 2749-2753, 3914-3923): 0 when encoded
+ *      as 0, else the one value RIC == enc - 1 (mod 2 * max_entries) in
+ *      [ins - max_entries + 1, ins + max_entries]; RIC <= 0: QHUFF_EPROTO;
+ *      RIC > ins: QHUFF_EBLOCKED (3980-3981: the section waits for inserts;
+ *      submit it again after more of them);
+ *   4. Base = RIC + DeltaBase, or RIC - DeltaBase - 1 when the sign bit is set
+ *      (4015-4022), in 64-bit two's complement; a line names Base - 1 - idx
+ *      (indexed and name reference, T = 0) or Base + idx (the post-base
+ *      forms).  QHUFF_EPROTO when that index is outside the section's window
+ *      (the entry is not there: 3070-3072, 3656-3658), when RIC = 0 and the
+ *      section has a dynamic line (3895), when RIC != 0 and no line names
+ *      RIC - 1 (3891-3894), or when a static index is >= 99.  A line's index
+ *      is not compared with RIC (the reference does not either);
+ *   5. QHUFF_OK.
+ * Never QHUFF_ENOTSUP.  The result equals the reference's whenever its
+ * modular ids are unambiguous, i.e. for references within MaxEntries of the
+ * insert count; where the reference's ids alias, the rule above (absolute
+ * indices) is the definition.
+ *
+ * A DYN descriptor: pos = the offset of its line's first byte (as STATIC; it
+ * occupies no wire bytes for the order rule), len = the string's bytes in the
+ * table, instr = its byte offset in tab->bytes, source = QHUFF_HSTR_DYN,
+ * static_id = QHUFF_STATIC_NONE.  kind[] of a line that names a dynamic entry
+ * has QHUFF_LINE_DYN OR-ed in (INDEXED|DYN = 4, NAMEREF|DYN = 5), its
+ * static_id[] is QHUFF_STATIC_NONE; an indexed dynamic line has N = 0, a
+ * dynamic name reference its line's N bit.
+ * Device form: device pointers, asynchronous, three launches on the scan's
+ * scratch timed as QHUFF_KIND_SCAN; tab is a host struct of device pointers
+ * (tab->bytes is not read).  The form of sec_win and off is THE CALLER'S
+ * DUTY: the walker clamps a window into [first, first + d] and takes a
+ * decreasing pair of offsets as an empty string, so nothing outside the
+ * arrays is read.  Host and _cpu forms: QHUFF_EINVAL also for a decreasing
+ * off, off[2d] < off[0] or a window outside the rule, QHUFF_ERANGE when
+ * first + d passes 2^32 - 1.
+ *
+ * qhuff_decode_headers_dyn: qhuff_decode_headers and the table's bytes
+ * (dyn_bytes, dyn_len of them; NULL with 0).  WIRE and STATIC strings as
+ * there; a DYN string is len bytes from dyn_bytes + instr; the max_len rule
+ * is unchanged (the name is string 2i whatever its source).  The kernel masks
+ * what it reads: source to two bits (3 behaves as WIRE), instr clamped to
+ * dyn_len, len to dyn_len - instr; it reads inside the 16-byte blocks that
+ * hold dyn_bytes[0 .. dyn_len) only.  `out` must hold
+ * qhuff_decode_headers_dyn_bound(wire_bytes, n, dyn_longest) = 8 * wire_bytes
+ * / 5 + max(76, dyn_longest) * n + 16 bytes, dyn_longest the table's longest
+ * name + value.  A tile is fast iff its output, dynamic bytes included, is at
+ * most 3008 bytes.
+ *
+ * qhuff_decode_headers_dyn_host: the whole path in one call, as
+ * qhuff_decode_headers_host: the wire bytes and the table go up once, the
+ * scan runs, the small results come back, the decode launch runs on the
+ * descriptors where they are; `out` holds qhuff_decode_headers_dyn_bound(wire
+ * bytes, max_hdrs, the table's longest entry).  The host's only loop is over
+ * the table's d entries. */
+#define QHUFF_FEATURE_DECODE_HEADERS_DYN 1
+#define QHUFF_EBLOCKED  (-11)  /* Required Insert Count above the inserts the
+                                  section may see                           */
+#define QHUFF_HSTR_DYN  2      /* qhuff_hstr.source: a dynamic entry's name
+                                  or value                                  */
+#define QHUFF_LINE_DYN  4      /* OR-ed into kind[]: the line names a dynamic
+                                  entry                                     */
+#define QHUFF_DYN_NONE  0xFFFFFFFFu
+
+struct qhuff_dyn_table {
+    const uint8_t  *bytes;     /* entries packed: name then value           */
+    const uint32_t *off;       /* off[2d + 1]                               */
+    uint32_t d;                /* entries held                              */
+    uint32_t first;            /* absolute index of entry 0                 */
+    uint32_t max_entries;      /* MaxEntries                                */
+};
+
+int qhuff_scan_headers_dyn(qhuff_ctx *ctx, const uint8_t *buf,
+                           const uint32_t *sec_off, uint32_t m,
+                           const struct qhuff_dyn_table *tab,
+                           const uint32_t *sec_win,
+                           struct qhuff_hstr *strs, uint32_t max_hdrs,
+                           uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                           uint8_t *static_id, uint8_t *hflags,
+                           uint32_t *dyn_id, void *stream);
+
+int qhuff_scan_headers_dyn_host(qhuff_ctx *ctx, const uint8_t *buf,
+                                const uint32_t *sec_off, uint32_t m,
+                                const struct qhuff_dyn_table *tab,
+                                const uint32_t *sec_win,
+                                struct qhuff_hstr *strs, uint32_t max_hdrs,
+                                uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                                uint8_t *static_id, uint8_t *hflags,
+                                uint32_t *dyn_id);
+
+int qhuff_scan_headers_dyn_cpu(const uint8_t *buf, const uint32_t *sec_off,
+                               uint32_t m, const struct qhuff_dyn_table *tab,
+                               const uint32_t *sec_win,
+                               struct qhuff_hstr *strs, uint32_t max_hdrs,
+                               uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                               uint8_t *static_id, uint8_t *hflags,
+                               uint32_t *dyn_id);
+
+uint64_t qhuff_decode_headers_dyn_bound(uint64_t wire_bytes, uint32_t n,
+                                        uint32_t dyn_longest);
+
+int qhuff_decode_headers_dyn(qhuff_ctx *ctx, const uint8_t *buf,
+                             const struct qhuff_hstr *strs, uint32_t n,
+                             uint32_t max_len, const uint8_t *dyn_bytes,
+                             uint32_t dyn_len, uint8_t *out, uint32_t *off,
+                             uint8_t *status, void *stream);
+
+int qhuff_decode_headers_dyn_host(qhuff_ctx *ctx, const uint8_t *buf,
+                                  const uint32_t *sec_off, uint32_t m,
+                                  const struct qhuff_dyn_table *tab,
+                                  const uint32_t *sec_win, uint32_t max_len,
+                                  uint32_t max_hdrs, uint32_t *hdr_off,
+                                  int32_t *rc, uint8_t *kind,
+                                  uint8_t *static_id, uint8_t *hflags,
+                                  uint32_t *dyn_id, uint8_t *out,
+                                  uint32_t *off, uint8_t *status,
+                                  uint32_t *name_hash,
+                                  uint32_t *nameval_hash);
+
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman
  * payload was precomputed by a QHUFF_ENC_PAYLOAD batch (huff, huff_len =

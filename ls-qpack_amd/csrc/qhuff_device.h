@@ -424,6 +424,8 @@ prof_stamp(const Coord &c, uint32_t it, int ph)
 //   w4  the first coop_decode call of the tile: [31:0] S, [47:32] trips of
 //       its B loop, bit 63 set once there was one
 //   w5  lanes whose payload the whole wave copied (encode: lm in emit)
+//   w6  the tile's output bytes that come from the dynamic table's entries
+//       (qhuff_decode_headers_dyn)
 #if defined(QH_PATH_TRACE) && defined(QHUFF_PROFILE)
 #error "QH_PATH_TRACE and QHUFF_PROFILE share Coord::prof: build one of them"
 #endif
@@ -434,6 +436,7 @@ struct PathTrace
     uint32_t units = 0, lone = 0, var = 0, dense = 0;
     uint32_t S = 0, rounds = 0, first = 0;
     uint64_t coop = 0, fail = 0, enc_coop = 0;
+    uint32_t dyn = 0;
     // coop_decode's S and B trips: the first call of the tile is kept
     __device__ __forceinline__ void first_call(uint32_t seg, uint32_t trips)
     {
@@ -456,6 +459,7 @@ struct PathTrace
         coop |= o.coop;
         fail |= o.fail;
         enc_coop |= o.enc_coop;
+        dyn += o.dyn;
     }
     // exit: 1 fast, 2 slot, 3 slow (every value wave-uniform; lane 0 stores)
     __device__ __forceinline__ void write(const Coord &c, uint32_t tile,
@@ -474,6 +478,7 @@ struct PathTrace
             r[4] = (uint64_t) S | (uint64_t) (rounds & 0xffff) << 32
                  | (uint64_t) first << 63;
             r[5] = enc_coop;
+            r[6] = dyn;
         }
     }
 };

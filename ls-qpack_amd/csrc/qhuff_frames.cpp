@@ -394,6 +394,56 @@ qhuff_scan_headers_cpu(const uint8_t *buf, const uint32_t *sec_off, uint32_t m,
     return hdr_off[m] > max_hdrs ? QHUFF_ERANGE : QHUFF_OK;
 }
 
+// qhuff_scan_headers_dyn's two passes in plain C++: the same walker with the
+// table and each section's window.
+extern "C" int
+qhuff_scan_headers_dyn_cpu(const uint8_t *buf, const uint32_t *sec_off,
+                           uint32_t m, const struct qhuff_dyn_table *tab,
+                           const uint32_t *sec_win, struct qhuff_hstr *strs,
+                           uint32_t max_hdrs, uint32_t *hdr_off, int32_t *rc,
+                           uint8_t *kind, uint8_t *static_id, uint8_t *hflags,
+                           uint32_t *dyn_id)
+{
+    namespace qs = qhuff::scan;
+    if (!hdr_off || !tab || (m && (!buf || !sec_off || !rc))
+            || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    for (uint32_t i = 0; i < m; ++i)
+        if (sec_off[i + 1] < sec_off[i])
+            return QHUFF_EINVAL;
+    uint32_t longest;
+    if (const int r = qs::dyn_check(tab, sec_win, m, &longest))
+        return r;
+    HostReader r{buf};
+    auto win = [&](uint32_t i) {
+        return qs::DynWin::of(tab->off, tab->d, tab->first, tab->max_entries,
+                              sec_win, i);
+    };
+    // the count pass
+    hdr_off[0] = 0;
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        qs::HdrDynCountSink s{0};
+        rc[i] = qs::walk_header_section(r, s, sec_off[i], sec_off[i + 1],
+                                        win(i));
+        hdr_off[i + 1] = hdr_off[i] + s.n;
+    }
+    // the write pass
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        const uint32_t first = hdr_off[i];
+        const uint32_t last = hdr_off[i + 1] < max_hdrs ? hdr_off[i + 1]
+                                                        : max_hdrs;
+        if (hdr_off[i + 1] == first || first >= last)
+            continue;
+        qs::HdrDynWriteSink w{{strs, kind, static_id, hflags, first, last},
+                              dyn_id};
+        (void) qs::walk_header_section(r, w, sec_off[i], sec_off[i + 1],
+                                       win(i));
+    }
+    return hdr_off[m] > max_hdrs ? QHUFF_ERANGE : QHUFF_OK;
+}
+
 // ---- the lookup kernel's source on the host (qhuff_lookup_impl.h) -----------
 //
 // qhuff_static_lookup in plain C++, header by header: the kernels' XXH32 and

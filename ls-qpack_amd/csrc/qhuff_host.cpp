@@ -1247,6 +1247,111 @@ qhuff_decode_headers(qhuff_ctx *c, const uint8_t *buf,
     });
 }
 
+// ---- ... against the dynamic table's entries (qhuff_hdrscan_dyn.hip,
+// qhuff_hdrdec_dyn.hip) --------------------------------------------------------
+
+// qhuff_scan_headers' frame over the walker with a table: the same scratch,
+// the same order, the same top launch.
+extern "C" int
+qhuff_scan_headers_dyn(qhuff_ctx *c, const uint8_t *buf,
+                       const uint32_t *sec_off, uint32_t m,
+                       const struct qhuff_dyn_table *tab,
+                       const uint32_t *sec_win, struct qhuff_hstr *strs,
+                       uint32_t max_hdrs, uint32_t *hdr_off, int32_t *rc,
+                       uint8_t *kind, uint8_t *static_id, uint8_t *hflags,
+                       uint32_t *dyn_id, void *stream)
+{
+    if (!c || !hdr_off || !tab || (tab->d && !tab->off)
+            || (m && (!buf || !sec_off || !rc)) || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(hdr_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    if (const int r = scan_prepare(c, m, st))
+        return r;
+    HdrScanDynArgs a;
+    a.h.buf = buf;
+    a.h.sec_off = sec_off;
+    a.h.strs = strs;
+    a.h.hdr_off = hdr_off;
+    a.h.rc = rc;
+    a.h.kind = kind;
+    a.h.static_id = static_id;
+    a.h.hflags = hflags;
+    a.h.cnt = c->scan_ws;
+    a.h.tot = c->scan_ws + c->scan_cap;
+    a.h.m = m;
+    a.h.max_hdrs = max_hdrs;
+    a.off = tab->off;
+    a.sec_win = sec_win;
+    a.dyn_id = dyn_id;
+    a.d = tab->d;
+    a.first = tab->first;
+    a.max_entries = tab->max_entries;
+    ScanArgs top = {};                   // (the top launch reads tot and m)
+    top.tot = a.h.tot;
+    top.m = m;
+    for (unsigned step = 0; step < 3; ++step)
+    {
+        const int r = timed(c, QHUFF_KIND_SCAN, "launch_hdrscan_dyn",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return step == 1 ? launch_scan(top, 1, st, e0, e1)
+                             : launch_hdrscan_dyn(a, step, st, e0, e1);
+        });
+        if (step || !r)
+        {
+            c->scan_stream = st;
+            c->scan_have = true;
+        }
+        if (r)
+            return r;
+    }
+    return QHUFF_OK;
+}
+
+extern "C" uint64_t
+qhuff_decode_headers_dyn_bound(uint64_t wire_bytes, uint32_t n,
+                               uint32_t dyn_longest)
+{
+    // qhuff_decode_headers_bound, a header's fixed text the longer of the
+    // longest static and the longest dynamic entry
+    return wire_bytes * 8 / 5 + (dyn_longest > 76 ? dyn_longest : 76ull) * n
+         + 16;
+}
+
+extern "C" int
+qhuff_decode_headers_dyn(qhuff_ctx *c, const uint8_t *buf,
+                         const struct qhuff_hstr *strs, uint32_t n,
+                         uint32_t max_len, const uint8_t *dyn_bytes,
+                         uint32_t dyn_len, uint8_t *out, uint32_t *off,
+                         uint8_t *status, void *stream)
+{
+    if (!c || !off || (n && (!buf || !strs || !out || !status))
+            || (dyn_len && !dyn_bytes))
+        return QHUFF_EINVAL;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    return tile_launch(c, 2 * n, decode_tile_strings(),
+                       hdrdec_dyn_waves_per_block(), c->dec_grid, off, st,
+                       [&](const Coord &k, uint32_t grid) -> int {
+        HdrDynArgs a;
+        a.w.d = dec_args(c, buf, (const uint32_t *) strs, out, off, status,
+                         2 * n, k);
+        a.w.max_len = max_len;
+        a.dyn = dyn_bytes;
+        a.dyn_len = dyn_len;
+        return timed(c, QHUFF_KIND_DECODE, "launch_hdrdec_dyn",
+                     [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_hdrdec_dyn(a, grid, st, e0, e1);
+        });
+    });
+}
+
 // ---- items encoded in one launch (qhuff_encwire.hip) -----------------------
 
 extern "C" uint64_t

@@ -1,6 +1,7 @@
 // qhuff_hostpath.cpp -- the pinned host-memory path of the C-ABI, buffer
 // registration and the per-string mirrors of the reference entry points.
 #include "qhuff_ctx.h"
+#include "qhuff_scan_impl.h"
 
 namespace qhuff {
 // qhuff_frames.cpp: a VALUE literal's static-table name length, or 0
@@ -1307,6 +1308,202 @@ qhuff_decode_headers_host(qhuff_ctx *c, const uint8_t *buf,
     if (n)
     {
         hdr_bytes_out(c, o, n, kind, static_id, hflags);
+        memcpy(status, H + o_st, 2ull * n);
+        if (name_hash)
+            memcpy(name_hash, H + o_h1, 4ull * n);
+        if (nameval_hash)
+            memcpy(nameval_hash, H + o_h2, 4ull * n);
+    }
+    return QHUFF_OK;
+}
+
+// ---- ... against the dynamic table's entries (qhuff_scan_headers_dyn) --------
+
+// hdr_staged with the table: its bytes, its offsets and the windows go up
+// with the wire bytes.  Stage layout: [16 | wire bytes | 16 | sec_off | table
+// bytes | table off | sec_win | hdr_off | rc | strs | kind | static_id |
+// hflags | dyn_id], the last five sized for max_hdrs; `extra` more bytes are
+// kept behind them, from o->h.end.
+struct DynStage
+{
+    HdrStage h;
+    size_t tab, did;                     // the table's bytes; dyn_id
+};
+
+static int
+dyn_staged(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+           uint32_t m, const struct qhuff_dyn_table *tab,
+           const uint32_t *sec_win, uint32_t max_hdrs, uint32_t *hdr_off,
+           int32_t *rc, uint64_t extra, DynStage *o)
+{
+    const uint64_t a0 = sec_off[0], bytes = (uint64_t) sec_off[m] - a0;
+    const uint64_t d = tab->d;
+    const uint64_t t0 = d ? tab->off[0] : 0, tb = d ? tab->off[2 * d] - t0 : 0;
+    const size_t o_so = up16(16 + bytes) + 16;
+    o->tab = o_so + up16(4ull * (m + 1));
+    const size_t o_to = o->tab + up16(tb);
+    const size_t o_sw = o_to + up16(4 * (2 * d + 1));
+    const size_t o_ho = o_sw + up16(sec_win ? 8ull * m : 0);
+    const size_t o_rc = o_ho + up16(4ull * (m + 1));
+    o->h.strs = o_rc + up16(4ull * m);
+    o->h.kind = o->h.strs + 32ull * max_hdrs;
+    o->h.id = o->h.kind + up16(max_hdrs);
+    o->h.hf = o->h.id + up16(max_hdrs);
+    o->did = o->h.hf + up16(max_hdrs);
+    o->h.end = o->did + up16(4ull * max_hdrs);
+    int r = stage_up(c, o->h.end + extra,
+                     {{buf + a0, bytes, 16}, {sec_off, 4ull * (m + 1), o_so},
+                      {d ? tab->bytes + t0 : nullptr, tb, o->tab},
+                      {tab->off, d ? 4 * (2 * d + 1) : 0, o_to},
+                      {sec_win, sec_win ? 8ull * m : 0, o_sw}},
+                     o_ho);
+    if (r)
+        return r;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    // (the kernels read the caller's offsets unchanged: the table's bytes are
+    // passed rebased by -off[0])
+    struct qhuff_dyn_table dev = *tab;
+    dev.bytes = D + o->tab - t0;
+    dev.off = d ? (const uint32_t *) (D + o_to) : nullptr;
+    r = qhuff_scan_headers_dyn(c, D + 16 - a0, (const uint32_t *) (D + o_so),
+                               m, &dev,
+                               sec_win ? (const uint32_t *) (D + o_sw)
+                                       : nullptr,
+                               (struct qhuff_hstr *) (D + o->h.strs), max_hdrs,
+                               (uint32_t *) (D + o_ho), (int32_t *) (D + o_rc),
+                               D + o->h.kind, D + o->h.id, D + o->h.hf,
+                               (uint32_t *) (D + o->did), c->own_stream);
+    if (r)
+        return r;
+    HIPCHK(c, hipMemcpyAsync(H + o_ho, D + o_ho, o->h.strs - o_ho,
+                             hipMemcpyDeviceToHost, c->own_stream));
+    HIPCHK(c, hipStreamSynchronize(c->own_stream));
+    memcpy(hdr_off, H + o_ho, 4ull * (m + 1));
+    memcpy(rc, H + o_rc, 4ull * m);
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_scan_headers_dyn_host(qhuff_ctx *c, const uint8_t *buf,
+                            const uint32_t *sec_off, uint32_t m,
+                            const struct qhuff_dyn_table *tab,
+                            const uint32_t *sec_win, struct qhuff_hstr *strs,
+                            uint32_t max_hdrs, uint32_t *hdr_off, int32_t *rc,
+                            uint8_t *kind, uint8_t *static_id,
+                            uint8_t *hflags, uint32_t *dyn_id)
+{
+    if (!hdr_args_ok(c, buf, sec_off, m, hdr_off, rc) || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    uint32_t longest;
+    if (const int r = scan::dyn_check(tab, sec_win, m, &longest))
+        return r;
+    if (m == 0)
+    {
+        hdr_off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    DynStage o;
+    int r = dyn_staged(c, buf, sec_off, m, tab, sec_win, max_hdrs, hdr_off,
+                       rc, 0, &o);
+    if (r)
+        return r;
+    const uint32_t n = hdr_off[m] < max_hdrs ? hdr_off[m] : max_hdrs;
+    if (n)
+    {
+        uint8_t *H = c->h_stage, *D = c->d_stage;
+        HIPCHK(c, hipMemcpyAsync(H + o.h.strs, D + o.h.strs, 32ull * n,
+                                 hipMemcpyDeviceToHost, c->own_stream));
+        HIPCHK(c, hipMemcpyAsync(H + o.h.kind, D + o.h.kind,
+                                 o.did + 4ull * n - o.h.kind,
+                                 hipMemcpyDeviceToHost, c->own_stream));
+        HIPCHK(c, hipStreamSynchronize(c->own_stream));
+        memcpy(strs, H + o.h.strs, 32ull * n);
+        hdr_bytes_out(c, o.h, n, kind, static_id, hflags);
+        if (dyn_id)
+            memcpy(dyn_id, H + o.did, 4ull * n);
+    }
+    return hdr_off[m] > max_hdrs ? QHUFF_ERANGE : QHUFF_OK;
+}
+
+// The whole path, as qhuff_decode_headers_host: dyn_staged, then
+// qhuff_decode_headers_dyn on the descriptors and on the table's bytes where
+// they lie.
+extern "C" int
+qhuff_decode_headers_dyn_host(qhuff_ctx *c, const uint8_t *buf,
+                              const uint32_t *sec_off, uint32_t m,
+                              const struct qhuff_dyn_table *tab,
+                              const uint32_t *sec_win, uint32_t max_len,
+                              uint32_t max_hdrs, uint32_t *hdr_off,
+                              int32_t *rc, uint8_t *kind, uint8_t *static_id,
+                              uint8_t *hflags, uint32_t *dyn_id, uint8_t *out,
+                              uint32_t *off, uint8_t *status,
+                              uint32_t *name_hash, uint32_t *nameval_hash)
+{
+    if (!off || !hdr_args_ok(c, buf, sec_off, m, hdr_off, rc)
+            || (max_hdrs && (!out || !status)))
+        return QHUFF_EINVAL;
+    if (max_hdrs > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    uint32_t longest;
+    if (const int r = scan::dyn_check(tab, sec_win, m, &longest))
+        return r;
+    if (m == 0)
+    {
+        hdr_off[0] = 0;
+        off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t bytes = (uint64_t) sec_off[m] - sec_off[0];
+    const uint64_t bound = qhuff_decode_headers_dyn_bound(bytes, max_hdrs,
+                                                          longest);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const uint64_t mh = max_hdrs;
+    DynStage o;
+    int r = dyn_staged(c, buf, sec_off, m, tab, sec_win, max_hdrs, hdr_off,
+                       rc,
+                       up16(4 * (2 * mh + 1)) + up16(2 * mh)
+                           + 2 * up16(4 * mh) + up16(bound),
+                       &o);
+    if (r)
+        return r;
+    const uint32_t n = hdr_off[m];
+    if (n > max_hdrs)
+        return QHUFF_ERANGE;
+    const size_t o_off = o.h.end;
+    const size_t o_st = o_off + up16(4 * (2ull * n + 1));
+    const size_t o_h1 = o_st + up16(2ull * n);
+    const size_t o_h2 = o_h1 + up16(4ull * n);
+    const size_t o_out = o_h2 + up16(4ull * n);
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    const uint32_t t0 = tab->d ? tab->off[0] : 0;
+    const uint32_t t1 = tab->d ? tab->off[2ull * tab->d] : 0;
+    // (dyn_bytes rebased as the scan's table: instr is an offset from
+    // tab->bytes; the kernel's blocks are those of [t0, t1) of it)
+    r = qhuff_decode_headers_dyn(c, D + 16 - sec_off[0],
+                                 (const struct qhuff_hstr *) (D + o.h.strs), n,
+                                 max_len, t1 ? D + o.tab - t0 : nullptr, t1,
+                                 D + o_out, (uint32_t *) (D + o_off),
+                                 D + o_st, c->own_stream);
+    if (r)
+        return r;
+    if (n && (name_hash || nameval_hash))
+    {
+        r = qhuff_xxh32_headers(c, D + o_out, (const uint32_t *) (D + o_off),
+                                n, QHUFF_XXH_SEED, (uint32_t *) (D + o_h1),
+                                (uint32_t *) (D + o_h2), c->own_stream);
+        if (r)
+            return r;
+    }
+    if ((r = stage_down(c, o.h.kind, o_off, o_out, 2 * n, out, off)))
+        return r;
+    if (n)
+    {
+        hdr_bytes_out(c, o.h, n, kind, static_id, hflags);
+        if (dyn_id)
+            memcpy(dyn_id, H + o.did, 4ull * n);
         memcpy(status, H + o_st, 2ull * n);
         if (name_hash)
             memcpy(name_hash, H + o_h1, 4ull * n);

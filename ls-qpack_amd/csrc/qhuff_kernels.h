@@ -105,6 +105,27 @@ struct HdrScanArgs
     uint32_t m, max_hdrs;
 };
 
+// the header scan against the dynamic table's entries
+// (qhuff_hdrscan_dyn.hip): the table's offsets and each section's window;
+// sec_win and dyn_id may be null
+struct HdrScanDynArgs
+{
+    HdrScanArgs h;
+    const uint32_t *off;         // 2d + 1, or null when d = 0
+    const uint32_t *sec_win;     // 2m, or null
+    uint32_t *dyn_id;            // max_hdrs, or null
+    uint32_t d, first, max_entries;
+};
+
+// header lists decoded with a third string source (qhuff_hdrdec_dyn.hip):
+// the table's bytes
+struct HdrDynArgs
+{
+    WireArgs w;
+    const uint8_t *dyn;          // dyn_len bytes, or null with 0
+    uint32_t dyn_len;
+};
+
 struct HashArgs
 {
     const uint8_t *in;
@@ -268,6 +289,15 @@ hipError_t launch_hdrscan(const HdrScanArgs &a, unsigned step, hipStream_t st,
 hipError_t launch_hdrdec(const WireArgs &a, uint32_t grid, hipStream_t st,
                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 int hdrdec_waves_per_block();
+// the same two pairs with the dynamic table's entries
+// (qhuff_hdrscan_dyn.hip, qhuff_hdrdec_dyn.hip)
+hipError_t launch_hdrscan_dyn(const HdrScanDynArgs &a, unsigned step,
+                              hipStream_t st, hipEvent_t ev0 = nullptr,
+                              hipEvent_t ev1 = nullptr);
+hipError_t launch_hdrdec_dyn(const HdrDynArgs &a, uint32_t grid,
+                             hipStream_t st, hipEvent_t ev0 = nullptr,
+                             hipEvent_t ev1 = nullptr);
+int hdrdec_dyn_waves_per_block();
 // items encoded in one launch (qhuff_encwire.hip): the encode arguments
 // (mode unused: every item has its own framing) and the n items
 hipError_t launch_encwire(const EncArgs &a, const ::qhuff_item *items,

@@ -358,25 +358,207 @@ struct HdrWriteSink
 
 constexpr uint32_t kHdrStaticEntries = 99;    // lsqpack.c:3021, 3130
 
+// ---- the dynamic table as a section's walk sees it (qhuff_scan_headers_dyn) --
+//
+// walk_header_lines / walk_header_section take a table policy.  NoDyn: there
+// is no table, a section that needs one is QHUFF_ENOTSUP (qhuff_scan_headers;
+// nothing of what follows is compiled into that walk).  DynWin: the table's
+// offsets and the section's window, for the read the reference's decoder does
+// per dynamic line (qdec_get_table_entry_abs, lsqpack.c:2768-2775;
+// header_out_dynamic_entry, 3060-3117; header_out_begin_dynamic_nameref).
+struct NoDyn
+{
+    static constexpr bool kOn = false;
+};
+
+struct DynWin
+{
+    static constexpr bool kOn = true;
+    const uint32_t *off;                 // the table's 2d + 1 offsets
+    uint32_t first, max_entries;
+    uint64_t lo, ins;                    // the window, inside [first, first + d]
+
+    // section s's window from sec_win (or the whole table), clamped into the
+    // table: whatever sec_win holds, an index inside [lo, ins) has its three
+    // offsets inside `off`
+    QH_HD static DynWin of(const uint32_t *off, uint32_t d, uint32_t first,
+                           uint32_t max_entries, const uint32_t *sec_win,
+                           uint64_t s)
+    {
+        DynWin w;
+        w.off = off;
+        w.first = first;
+        w.max_entries = max_entries;
+        const uint64_t t0 = first, t1 = (uint64_t) first + d;
+        w.lo = sec_win ? sec_win[2 * s] : t0;
+        w.ins = sec_win ? sec_win[2 * s + 1] : t1;
+        w.lo = w.lo < t0 ? t0 : w.lo;
+        w.ins = w.ins > t1 ? t1 : w.ins;
+        return w;
+    }
+};
+
+// the host forms' check of a table and of m windows: QHUFF_OK, QHUFF_EINVAL
+// (a null pointer with d != 0, decreasing offsets, a window outside the
+// rule) or QHUFF_ERANGE (first + d passes 2^32 - 1); *longest = the longest
+// name + value
+inline int
+dyn_check(const ::qhuff_dyn_table *t, const uint32_t *sec_win, uint32_t m,
+          uint32_t *longest)
+{
+    *longest = 0;
+    if (!t || (t->d && (!t->off || !t->bytes)))
+        return QHUFF_EINVAL;
+    if ((uint64_t) t->first + t->d > 0xffffffffull)
+        return QHUFF_ERANGE;
+    for (uint64_t i = 0; i < 2ull * t->d; ++i)
+        if (t->off[i + 1] < t->off[i])
+            return QHUFF_EINVAL;
+    for (uint64_t k = 0; k < t->d; ++k)
+    {
+        const uint32_t l = t->off[2 * k + 2] - t->off[2 * k];
+        *longest = l > *longest ? l : *longest;
+    }
+    for (uint64_t s = 0; sec_win && s < m; ++s)
+        if (sec_win[2 * s] < t->first || sec_win[2 * s + 1] < sec_win[2 * s]
+                || sec_win[2 * s + 1] > t->first + t->d)
+            return QHUFF_EINVAL;
+    return QHUFF_OK;
+}
+
+QH_HD inline ::qhuff_hstr
+hstr_dyn(uint32_t toff, uint32_t len, uint32_t kind, uint32_t at)
+{
+    ::qhuff_hstr d;
+    d.pos = at;
+    d.len = len;
+    d.huffman = 0;
+    d.source = QHUFF_HSTR_DYN;
+    d.kind = (uint8_t) kind;
+    d.static_id = QHUFF_STATIC_NONE;
+    d.instr = toff;
+    return d;
+}
+
+// HdrCountSink for a walk with a table: dyn_line(kind, abs, nbit, at, value,
+// table) takes a line that names the dynamic entry `abs`
+struct HdrDynCountSink
+{
+    uint32_t n;
+    QH_HD void line(uint32_t, uint32_t, uint32_t, uint32_t, const Lit &,
+                    const Lit &)
+    {
+        ++n;
+    }
+    QH_HD void dyn_line(uint32_t, uint64_t, uint32_t, uint32_t, const Lit &,
+                        const DynWin &)
+    {
+        ++n;
+    }
+};
+
+// HdrWriteSink for a walk with a table: the entry's name and value come from
+// its three offsets (a decreasing pair counts as an empty string)
+struct HdrDynWriteSink
+{
+    HdrWriteSink w;
+    uint32_t *dyn_id;
+    QH_HD void line(uint32_t k, uint32_t id, uint32_t nbit, uint32_t at,
+                    const Lit &name, const Lit &value)
+    {
+        if (w.n < w.limit && dyn_id)
+            dyn_id[w.n] = QHUFF_DYN_NONE;
+        w.line(k, id, nbit, at, name, value);
+    }
+    QH_HD void dyn_line(uint32_t k, uint64_t abs, uint32_t nbit, uint32_t at,
+                        const Lit &value, const DynWin &t)
+    {
+        if (w.n < w.limit)
+        {
+            const uint64_t e = 2 * (abs - t.first);
+            const uint32_t o0 = t.off[e], o1 = t.off[e + 1], o2 = t.off[e + 2];
+            const uint64_t i = 2 * (uint64_t) w.n;
+            w.strs[i] = hstr_dyn(o0, o1 > o0 ? o1 - o0 : 0u, QHUFF_LIT_NAME, at);
+            w.strs[i + 1] = k == QHUFF_LINE_INDEXED
+                ? hstr_dyn(o1, o2 > o1 ? o2 - o1 : 0u, QHUFF_LIT_VALUE, at)
+                : hstr_wire(value, QHUFF_LIT_VALUE, at);
+            if (w.kind)
+                w.kind[w.n] = (uint8_t) (k | QHUFF_LINE_DYN);
+            if (w.static_id)
+                w.static_id[w.n] = QHUFF_STATIC_NONE;
+            if (w.hflags)
+                w.hflags[w.n] = (uint8_t) (nbit ? QHUFF_HDR_NEVER_INDEX : 0);
+            if (dyn_id)
+                dyn_id[w.n] = (uint32_t) abs;
+        }
+        ++w.n;
+    }
+};
+
+// the sink's count, whichever sink
+QH_HD inline uint32_t &sink_n(HdrCountSink &s) { return s.n; }
+QH_HD inline uint32_t &sink_n(HdrWriteSink &s) { return s.n; }
+QH_HD inline uint32_t &sink_n(HdrDynCountSink &s) { return s.n; }
+QH_HD inline uint32_t &sink_n(HdrDynWriteSink &s) { return s.w.n; }
+
 // One complete field section in [p, end) walked for its header lines: the
 // framing result of walk_field_section (0, -1 or -2) -- the walk goes on to
 // the section's end whatever the lines mean, so that a framing error wins --
-// and in *flags bit 0: the section needs the dynamic table (Required Insert
-// Count != 0 or a dynamic form), bit 1: a static index >= 99.  Lines are
-// reported until the first flag is raised.
-template <class R, class S>
+// and in *flags
+//   bit 0  the section needs the dynamic table and there is none (NoDyn:
+//          Required Insert Count != 0 or a dynamic form);
+//   bit 1  a static index >= 99; with a table also: a dynamic line with a
+//          Required Insert Count of 0 or an index outside the window, or no
+//          line that names Required Insert Count - 1;
+//   bit 2  (table) the encoded Required Insert Count is above 2 * MaxEntries,
+//          or the count it stands for is not positive;
+//   bit 3  (table) the Required Insert Count is above the section's inserts.
+// Lines are reported until the first flag is raised.
+template <class R, class S, class D>
 QH_HD inline int
-walk_header_lines(R &r, S &s, uint32_t p, uint32_t end, uint32_t *flags)
+walk_header_lines(R &r, S &s, uint32_t p, uint32_t end, uint32_t *flags,
+                  const D &dy)
 {
     const uint32_t max_str = QHUFF_MAX_STRLEN;
     uint64_t ric, v;
     int rc;
     uint32_t f = 0;
     *flags = 0;
-    // (the Delta Base and its sign are read and ignored)
-    if ((rc = dec_int(r, &p, end, 8, &ric)) || (rc = dec_int(r, &p, end, 7, &v)))
+    // (no table: the Delta Base and its sign are read and ignored)
+    if ((rc = dec_int(r, &p, end, 8, &ric)))
         return rc;
-    if (ric)
+    [[maybe_unused]] bool sign = false;
+    if constexpr (D::kOn)
+        sign = p < end && (r.get(p) & 0x80);
+    if ((rc = dec_int(r, &p, end, 7, &v)))
+        return rc;
+    [[maybe_unused]] uint64_t base = 0;
+    [[maybe_unused]] bool named = false;     // a line named ric - 1
+    if constexpr (D::kOn)
+    {
+        // the Required Insert Count the encoded one stands for (RFC 9204
+        // 4.5.1.1; the reference's modular ids, lsqpack.c:2749-2753,
+        // 3914-3923, 3973-3981): the value == ric - 1 (mod 2 * MaxEntries)
+        // in [ins - MaxEntries + 1, ins + MaxEntries]
+        const int64_t me = dy.max_entries, full = 2 * me;
+        if (ric > (uint64_t) full)
+            f |= 4;
+        else if (ric)
+        {
+            const int64_t lo = (int64_t) dy.ins - me + 1;
+            int64_t m = ((int64_t) ric - 1 - lo) % full;
+            m += m < 0 ? full : 0;
+            const int64_t req = lo + m;
+            if (req <= 0)
+                f |= 4;
+            else if ((uint64_t) req > dy.ins)
+                f |= 8;
+            ric = (uint64_t) req;
+        }
+        // (lsqpack.c:4015-4022; two's complement, 64 bits)
+        base = sign ? ric - v - 1 : ric + v;
+    }
+    else if (ric)
         f |= 1;
     while (p < end)
     {
@@ -384,6 +566,7 @@ walk_header_lines(R &r, S &s, uint32_t p, uint32_t end, uint32_t *flags)
         const uint32_t at = p;
         uint32_t idx = 0, k = QHUFF_LINE_LITERAL, nbit = 0;
         bool dyn = false;
+        [[maybe_unused]] bool post = false;
         LitCatch name, value;
         name.l = Lit();
         value.l = Lit();
@@ -415,6 +598,11 @@ walk_header_lines(R &r, S &s, uint32_t p, uint32_t end, uint32_t *flags)
         {
             rc = dec_int24(r, &p, end, 4, &idx);
             dyn = true;
+            if constexpr (D::kOn)
+            {
+                k = QHUFF_LINE_INDEXED;
+                post = true;
+            }
         }
         else                                   // 0000Nxxx post-base name ref
         {
@@ -423,9 +611,32 @@ walk_header_lines(R &r, S &s, uint32_t p, uint32_t end, uint32_t *flags)
                 rc = literal(r, value, &p, end, 7, QHUFF_LIT_VALUE, at,
                              max_str);
             dyn = true;
+            if constexpr (D::kOn)
+            {
+                k = QHUFF_LINE_NAMEREF;
+                nbit = b & 0x08;
+                post = true;
+            }
         }
         if (rc)
             return rc;
+        if constexpr (D::kOn)
+        {
+            if (dyn)
+            {
+                // (an index below 0 is a large one here: outside any window)
+                const uint64_t abs = post ? base + idx : base - 1 - idx;
+                if (!ric || abs < dy.lo || abs >= dy.ins)
+                    f |= 2;
+                else
+                {
+                    named |= abs == ric - 1;
+                    if (!f)
+                        s.dyn_line(k, abs, nbit, at, value.l, dy);
+                }
+                continue;
+            }
+        }
         if (dyn)
             f |= 1;
         else if (k != QHUFF_LINE_LITERAL && idx >= kHdrStaticEntries)
@@ -433,26 +644,39 @@ walk_header_lines(R &r, S &s, uint32_t p, uint32_t end, uint32_t *flags)
         if (!f)
             s.line(k, idx, nbit, at, name.l, value.l);
     }
+    if constexpr (D::kOn)
+        if (ric && !named)
+            f |= 2;
     *flags = f;
     return 0;
 }
 
-// One section [a, b): its QHUFF_* result in the order of qhuff_scan_headers;
-// the sink's n has advanced by the section's headers, or is back where it
-// was when the result is not QHUFF_OK.
+// One section [a, b): its QHUFF_* result in the order of qhuff_scan_headers
+// (NoDyn) or of qhuff_scan_headers_dyn; the sink's n has advanced by the
+// section's headers, or is back where it was when the result is not QHUFF_OK.
+template <class R, class S, class D>
+QH_HD inline int
+walk_header_section(R &r, S &s, uint32_t a, uint32_t b, const D &dy)
+{
+    const uint32_t n0 = sink_n(s);
+    uint32_t flags;
+    const int rc = walk_header_lines(r, s, a, b, &flags, dy);
+    if (!rc && !flags)
+        return QHUFF_OK;
+    sink_n(s) = n0;
+    if constexpr (D::kOn)
+        if (!rc && (flags & 12))
+            return (flags & 4) ? QHUFF_EPROTO : QHUFF_EBLOCKED;
+    return rc == -1 ? QHUFF_ETRUNC
+         : rc ? QHUFF_EPROTO
+         : (flags & 1) ? QHUFF_ENOTSUP : QHUFF_EPROTO;
+}
+
 template <class R, class S>
 QH_HD inline int
 walk_header_section(R &r, S &s, uint32_t a, uint32_t b)
 {
-    const uint32_t n0 = s.n;
-    uint32_t flags;
-    const int rc = walk_header_lines(r, s, a, b, &flags);
-    if (!rc && !flags)
-        return QHUFF_OK;
-    s.n = n0;
-    return rc == -1 ? QHUFF_ETRUNC
-         : rc ? QHUFF_EPROTO
-         : (flags & 1) ? QHUFF_ENOTSUP : QHUFF_EPROTO;
+    return walk_header_section(r, s, a, b, NoDyn());
 }
 
 }  // namespace scan

@@ -58,6 +58,9 @@ EXPORTS = (
     "qhuff_scan_headers", "qhuff_scan_headers_host", "qhuff_scan_headers_cpu",
     "qhuff_decode_headers_bound", "qhuff_decode_headers",
     "qhuff_decode_headers_host",
+    "qhuff_scan_headers_dyn", "qhuff_scan_headers_dyn_host",
+    "qhuff_scan_headers_dyn_cpu", "qhuff_decode_headers_dyn_bound",
+    "qhuff_decode_headers_dyn", "qhuff_decode_headers_dyn_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -65,6 +68,10 @@ EXPORTS = (
 )
 EPROTO, ETRUNC = -71, -61
 ENOTSUP = -95                             # QHUFF_ENOTSUP (qhuff_scan_headers)
+EBLOCKED = -11                            # QHUFF_EBLOCKED (qhuff_scan_headers_dyn)
+HSTR_WIRE, HSTR_STATIC, HSTR_DYN = 0, 1, 2    # QHUFF_HSTR_*
+LINE_DYN = 4                              # QHUFF_LINE_DYN
+DYN_NONE = 0xFFFFFFFF                     # QHUFF_DYN_NONE
 HSTR_WIRE, HSTR_STATIC = 0, 1             # QHUFF_HSTR_*
 TIMING_SLOTS = 256                        # QHUFF_TIMING_SLOTS
 KIND_ENCODE, KIND_DECODE, KIND_HASH = 0, 1, 2
@@ -371,6 +378,32 @@ def lib():
         L.qhuff_decode_headers.restype = C.c_int
         L.qhuff_decode_headers.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32,
                                            vp, u32p, vp, vp]
+        dtp = C.POINTER(DynTable)
+        L.qhuff_scan_headers_dyn.restype = C.c_int
+        L.qhuff_scan_headers_dyn.argtypes = [vp, vp, vp, C.c_uint32, dtp, vp,
+                                             vp, C.c_uint32, vp, vp, vp, vp,
+                                             vp, vp, vp]
+        L.qhuff_scan_headers_dyn_host.restype = C.c_int
+        L.qhuff_scan_headers_dyn_host.argtypes = [vp, vp, u32p, C.c_uint32,
+                                                  dtp, vp, vp, C.c_uint32, vp,
+                                                  vp, vp, vp, vp, vp]
+        L.qhuff_scan_headers_dyn_cpu.restype = C.c_int
+        L.qhuff_scan_headers_dyn_cpu.argtypes = [vp, u32p, C.c_uint32, dtp,
+                                                 vp, vp, C.c_uint32, vp, vp,
+                                                 vp, vp, vp, vp]
+        L.qhuff_decode_headers_dyn_bound.restype = C.c_uint64
+        L.qhuff_decode_headers_dyn_bound.argtypes = [C.c_uint64, C.c_uint32,
+                                                     C.c_uint32]
+        L.qhuff_decode_headers_dyn.restype = C.c_int
+        L.qhuff_decode_headers_dyn.argtypes = [vp, vp, vp, C.c_uint32,
+                                               C.c_uint32, vp, C.c_uint32,
+                                               vp, vp, vp, vp]
+        L.qhuff_decode_headers_dyn_host.restype = C.c_int
+        L.qhuff_decode_headers_dyn_host.argtypes = [vp, vp, u32p, C.c_uint32,
+                                                    dtp, vp, C.c_uint32,
+                                                    C.c_uint32, vp, vp, vp,
+                                                    vp, vp, vp, vp, vp, vp,
+                                                    vp, vp]
         L.qhuff_decode_headers_host.restype = C.c_int
         L.qhuff_decode_headers_host.argtypes = [vp, vp, u32p, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, u32p,
@@ -550,6 +583,66 @@ def scan_headers_cpu(buf, sec_off, max_hdrs=None):
         raise QhuffError("qhuff_scan_headers_cpu failed: %d" % ret)
     n = min(int(hdr_off[-1]), max_hdrs)
     return ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n], hf[:n]
+
+
+class DynTable(C.Structure):
+    """struct qhuff_dyn_table"""
+    _fields_ = [("bytes", C.c_void_p), ("off", C.c_void_p), ("d", C.c_uint32),
+                ("first", C.c_uint32), ("max_entries", C.c_uint32)]
+
+
+def decode_headers_dyn_bound(wire_bytes, n, dyn_longest):
+    return int(lib().qhuff_decode_headers_dyn_bound(wire_bytes, n,
+                                                    dyn_longest))
+
+
+def dyn_table_host(data, off, first=0, max_entries=0):
+    """The dynamic table's entries as host arrays -> (DynTable, the arrays it
+    points to): data the packed names and values, off uint32 [2d + 1] (None
+    or one entry: d = 0), entry k the absolute index first + k."""
+    import numpy as np
+    off = np.zeros(1, np.uint32) if off is None else \
+        np.ascontiguousarray(off, dtype=np.uint32)
+    d = (len(off) - 1) // 2
+    data = np.ascontiguousarray(data if data is not None else [],
+                                dtype=np.uint8)
+    if not len(data):
+        data = np.zeros(1, dtype=np.uint8)   # (d entries, all empty)
+    t = DynTable(_np_ptr(data) if d else None,
+                 _np_ptr(off) if d else None, d, first, max_entries)
+    return t, (data, off)
+
+
+def _sec_win_host(sec_win):
+    import numpy as np
+    return None if sec_win is None else \
+        np.ascontiguousarray(sec_win, dtype=np.uint32).reshape(-1)
+
+
+def scan_headers_dyn_cpu(buf, sec_off, table, sec_win=None, max_hdrs=None):
+    """qhuff_scan_headers_dyn_cpu: scan_headers_cpu against the dynamic
+    table's entries.  table: (data, off, first, max_entries) host arrays as
+    dyn_table_host takes them; sec_win: uint32 [2m] or None -> (ret, strs,
+    hdr_off, rc, kind, static_id, hflags, dyn_id); ret OK, ERANGE, or EINVAL /
+    ERANGE of the argument checks (the arrays then as they were made)."""
+    import numpy as np
+    if max_hdrs is None:
+        max_hdrs = int(scan_headers_dyn_cpu(buf, sec_off, table, sec_win,
+                                            0)[2][-1])
+    buf, sec_off, m, strs, hdr_off, rc, kind, sid, hf = \
+        _headers_host_args(buf, sec_off, max_hdrs)
+    did = np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+    t, keep = dyn_table_host(*table)
+    win = _sec_win_host(sec_win)
+    ret = lib().qhuff_scan_headers_dyn_cpu(
+        _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off), m, C.byref(t),
+        _np_ptr(win) if win is not None else None, _np_ptr(strs), max_hdrs,
+        _np_ptr(hdr_off), _np_ptr(rc), _np_ptr(kind), _np_ptr(sid),
+        _np_ptr(hf), _np_ptr(did))
+    del keep
+    n = min(int(hdr_off[-1]), max_hdrs)
+    return (ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n], hf[:n],
+            did[:n])
 
 
 def hstrs_array(strs):
@@ -1249,6 +1342,138 @@ class Codec:
         self._check(ret, "qhuff_decode_headers_host")
         n = int(hdr_off[-1])
         res = (ret, hdr_off, rc[:m], kind[:n], sid[:n], hf[:n],
+               out[:off[2 * n]], off[:2 * n + 1], status[:2 * n])
+        return res + ((h1[:n], h2[:n]) if hashes else ())
+
+    # ... against the dynamic table's entries --------------------------------
+    def scan_headers_dyn_into(self, buf, sec_off, m, tab_off, d, first,
+                              max_entries, sec_win, strs, max_hdrs, hdr_off,
+                              rc, kind=None, static_id=None, hflags=None,
+                              dyn_id=None, stream=None):
+        """qhuff_scan_headers_dyn: all device tensors; tab_off the table's
+        int32 [2d + 1] offsets (None with d = 0), sec_win int32 [2m] or
+        None; kind, static_id, hflags and dyn_id may be None."""
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        t = DynTable(None, opt(tab_off) if d else None, d, first, max_entries)
+        r = lib().qhuff_scan_headers_dyn(
+            self._ctx, buf.data_ptr(), sec_off.data_ptr(), m, C.byref(t),
+            opt(sec_win), opt(strs), max_hdrs, hdr_off.data_ptr(),
+            rc.data_ptr(), opt(kind), opt(static_id), opt(hflags),
+            opt(dyn_id), self._stream(stream))
+        self._check(r, "qhuff_scan_headers_dyn")
+
+    def scan_headers_dyn(self, buf, sec_off, tab_off, first, max_entries,
+                         sec_win, max_hdrs, stream=None):
+        """scan_headers against the table -> (strs, hdr_off, rc, kind,
+        static_id, hflags, dyn_id int32 [max_hdrs]) device tensors."""
+        import torch
+        m = sec_off.numel() - 1
+        dev = buf.device
+        k = max(max_hdrs, 1)
+        strs = torch.empty(32 * k, dtype=torch.uint8, device=dev)
+        hdr_off = torch.empty(m + 1, dtype=torch.int32, device=dev)
+        rc = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        kind, sid, hf = (torch.empty(k, dtype=torch.uint8, device=dev)
+                         for _ in range(3))
+        did = torch.empty(k, dtype=torch.int32, device=dev)
+        d = (tab_off.numel() - 1) // 2 if tab_off is not None else 0
+        self.scan_headers_dyn_into(buf, sec_off, m, tab_off, d, first,
+                                   max_entries, sec_win, strs, max_hdrs,
+                                   hdr_off, rc, kind, sid, hf, did, stream)
+        return strs, hdr_off, rc[:m], kind, sid, hf, did
+
+    def scan_headers_dyn_host(self, buf, sec_off, table, sec_win=None,
+                              max_hdrs=None):
+        """qhuff_scan_headers_dyn_host over host arrays -> as
+        scan_headers_dyn_cpu."""
+        import numpy as np
+        if max_hdrs is None:
+            max_hdrs = int(self.scan_headers_dyn_host(buf, sec_off, table,
+                                                      sec_win, 0)[2][-1])
+        buf, sec_off, m, strs, hdr_off, rc, kind, sid, hf = \
+            _headers_host_args(buf, sec_off, max_hdrs)
+        did = np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+        t, keep = dyn_table_host(*table)
+        win = _sec_win_host(sec_win)
+        ret = lib().qhuff_scan_headers_dyn_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, C.byref(t), _np_ptr(win) if win is not None else None,
+            _np_ptr(strs), max_hdrs, _np_ptr(hdr_off), _np_ptr(rc),
+            _np_ptr(kind), _np_ptr(sid), _np_ptr(hf), _np_ptr(did))
+        del keep
+        if ret not in (ERANGE, EINVAL):
+            self._check(ret, "qhuff_scan_headers_dyn_host")
+        n = min(int(hdr_off[-1]), max_hdrs)
+        return (ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n],
+                hf[:n], did[:n])
+
+    def decode_headers_dyn_into(self, buf, strs, n, max_len, dyn, dyn_len,
+                                out, off, status, stream=None):
+        """qhuff_decode_headers_dyn: decode_headers_into and the table's
+        bytes (a uint8 device tensor, or None with dyn_len 0)."""
+        rc = lib().qhuff_decode_headers_dyn(
+            self._ctx, buf.data_ptr(), strs.data_ptr(), n, max_len or 0,
+            dyn.data_ptr() if dyn is not None and dyn_len else None, dyn_len,
+            out.data_ptr(), off.data_ptr(), status.data_ptr(),
+            self._stream(stream))
+        self._check(rc, "qhuff_decode_headers_dyn")
+
+    def decode_headers_dyn(self, buf, strs, n, dyn, dyn_longest, max_len=None,
+                           stream=None, wire_bytes=None):
+        """decode_headers with the table's bytes `dyn` (uint8 cuda tensor or
+        None); dyn_longest: its longest name + value (the bound)."""
+        import torch
+        if wire_bytes is None:
+            wire_bytes = int(buf.numel())
+        out = torch.empty(decode_headers_dyn_bound(wire_bytes, n, dyn_longest),
+                          dtype=torch.uint8, device=buf.device)
+        off = torch.empty(2 * n + 1, dtype=torch.int32, device=buf.device)
+        status = torch.empty(max(2 * n, 1), dtype=torch.uint8,
+                             device=buf.device)
+        self.decode_headers_dyn_into(buf, strs, n, max_len, dyn,
+                                     int(dyn.numel()) if dyn is not None
+                                     else 0, out, off, status, stream)
+        return out, off, status[:2 * n]
+
+    def decode_headers_dyn_host(self, buf, sec_off, table, sec_win=None,
+                                max_len=None, max_hdrs=None, hashes=False):
+        """qhuff_decode_headers_dyn_host: scan and decode against the table
+        in one call -> (ret, hdr_off, rc, kind, static_id, hflags, dyn_id,
+        out, off, status[, name_hash, nameval_hash]); ret OK, or ERANGE
+        (hdr_off[-1] > max_hdrs: nothing decoded, the arrays after rc
+        None)."""
+        import numpy as np
+        if max_hdrs is None:
+            max_hdrs = int(self.scan_headers_dyn_host(buf, sec_off, table,
+                                                      sec_win, 0)[2][-1])
+        buf, sec_off, m, _, hdr_off, rc, kind, sid, hf = \
+            _headers_host_args(buf, sec_off, max_hdrs)
+        did = np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+        t, keep = dyn_table_host(*table)
+        toff = keep[1]
+        longest = int((toff[2::2] - toff[:-2:2]).max()) if t.d else 0
+        win = _sec_win_host(sec_win)
+        wire = max(int(sec_off[-1]) - int(sec_off[0]), 0)
+        out = np.zeros(decode_headers_dyn_bound(wire, max_hdrs, longest),
+                       dtype=np.uint8)
+        off = np.zeros(2 * max_hdrs + 1, dtype=np.uint32)
+        status = np.zeros(max(2 * max_hdrs, 1), dtype=np.uint8)
+        h1, h2 = (np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+                  for _ in range(2))
+        ret = lib().qhuff_decode_headers_dyn_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, C.byref(t), _np_ptr(win) if win is not None else None,
+            max_len or 0, max_hdrs, _np_ptr(hdr_off), _np_ptr(rc),
+            _np_ptr(kind), _np_ptr(sid), _np_ptr(hf), _np_ptr(did),
+            _np_ptr(out), _np_ptr(off), _np_ptr(status),
+            _np_ptr(h1) if hashes else None, _np_ptr(h2) if hashes else None)
+        del keep
+        tail = (None,) * (9 if hashes else 7)
+        if ret == ERANGE:
+            return (ret, hdr_off, rc[:m]) + tail
+        self._check(ret, "qhuff_decode_headers_dyn_host")
+        n = int(hdr_off[-1])
+        res = (ret, hdr_off, rc[:m], kind[:n], sid[:n], hf[:n], did[:n],
                out[:off[2 * n]], off[:2 * n + 1], status[:2 * n])
         return res + ((h1[:n], h2[:n]) if hashes else ())
 
