@@ -1134,6 +1134,162 @@ int qhuff_decode_headers_dyn_host(qhuff_ctx *ctx, const uint8_t *buf,
                                   uint32_t *name_hash,
                                   uint32_t *nameval_hash);
 
+/* ---- header lists encoded to field sections against the dynamic table ------
+ * qhuff_encode_headers writes what lsqpack_enc_encode(..., LQEF_NO_DYN)
+ * writes.  These calls write what it writes with the table in use and
+ * LQEF_NO_INDEX: nothing is inserted, the header is looked up in the static
+ * table and among the dynamic entries, and a line is written
+ * (lsqpack.c:1671-1930 with index = 0).  Encoding against a given table is a
+ * read of that table, as decoding is: with the entries at hand the decision
+ * is per header and stateless; only a section's prefix depends on all of its
+ * lines.  Inserting, the encoder stream, the history, risked-stream
+ * accounting and duplication stay with the host.
+ * QHUFF_FEATURE_ENCODE_HEADERS_DYN and the symbols announce it (the ABI
+ * version is unchanged); the calls above behave as before.
+ *
+ * Inputs: those of qhuff_encode_headers, and
+ *   tab       the table, as in the _dyn decode calls (in the device form a
+ *             host struct of device pointers; here tab->bytes is read);
+ *             d = 0 with null pointers is legal;
+ *   sec_win   2m entries, or NULL: section s may name the entries with an
+ *             absolute index in [sec_win[2s], sec_win[2s + 1]).  The low
+ *             edge is the caller's "not draining" bound
+ *             (qenc_entry_is_draining, lsqpack.c:1528), the high edge the
+ *             insert count it may reference: qpe_max_acked_id when it may
+ *             not risk, else the insert count (1790-1791, 1879-1881).  The
+ *             rule: first <= lo <= hi <= first + d and, when max_entries is
+ *             not 0, hi - lo <= max_entries (else the encoded Required
+ *             Insert Count is ambiguous).  NULL: every section sees [first,
+ *             first + d);
+ *   sec_base  m entries, or NULL: the section's Base, the reference's
+ *             qpe_cur_header.base_idx -- the insert count at
+ *             lsqpack_enc_start_header (lsqpack.c:1106).  Any value <= first
+ *             + d (below `first`: every entry is named post-base).  NULL:
+ *             sec_win[2s + 1].  An entry with abs >= Base is named by the
+ *             post-base forms, as the reference's EHA_INDEXED_NEW /
+ *             EHA_LIT_WITH_NAME_NEW name an entry inserted during the
+ *             section (2040-2050, 2077-2092).
+ * Per header the line is chosen in the reference's order:
+ *   1. name and value are a static entry (find_in_static_full, 1687-1715):
+ *      QHUFF_LINE_INDEXED, as qhuff_encode_headers;
+ *   2. name and value, bytes compared, are an entry of the window (the walk
+ *      of 1743-1834): QHUFF_LINE_INDEXED | QHUFF_LINE_DYN.  Of several equal
+ *      entries the HIGHEST absolute index: the reference takes the newer of
+ *      its two candidates (1801-1824); its tables never hold more than two,
+ *      for more this rule is the definition.  0x80 | (Base - 1 - abs) on 6
+ *      bits (EHA_INDEXED_DYN, 2051-2060), or post-base 0x10 | (abs - Base) on
+ *      4 bits (2042-2050); no N bit;
+ *   3. the name is a static entry's (lsqpack_find_in_static_headers,
+ *      1835-1866): QHUFF_LINE_NAMEREF, as qhuff_encode_headers;
+ *   4. the name is that of an entry of the window: QHUFF_LINE_NAMEREF |
+ *      QHUFF_LINE_DYN.  The LOWEST absolute index in the window: the
+ *      reference's bucket lists are appended at the tail and it takes the
+ *      first hit (1877-1901).  0x40 | N << 5 with the index on 4 bits
+ *      (EHA_LIT_WITH_NAME_DYN, 2093-2109), or post-base 0x00 | N << 3 on 3
+ *      bits (2079-2092); then lsqpack_enc_enc_str(7, value);
+ *   5. QHUFF_LINE_LITERAL, as qhuff_encode_headers.
+ * The section's prefix (lsqpack_enc_end_header, lsqpack.c:1267-1298): the
+ * Required Insert Count RIC = 1 + the largest absolute index any of its lines
+ * named, 0 if none; encoded RIC % (2 * max_entries) + 1 (0 for 0) on 8 bits;
+ * then S = 0 and Base - RIC on 7 bits when Base >= RIC, else S = 1 and RIC -
+ * Base - 1.  RIC = 0 gives 00 00 whatever Base is.  max_entries = 0 or an
+ * empty window: no dynamic lines.
+ *
+ * Outputs: those of qhuff_encode_headers and dyn_id[n] (the absolute index
+ * the line named, or QHUFF_DYN_NONE; may be NULL).  kind and static_id follow
+ * the _dyn scan's conventions (static_id = QHUFF_STATIC_NONE on a dynamic
+ * line), so qhuff_decode_headers_dyn_host on the output with the same table
+ * and windows returns the same three arrays and the header lists.  `out`
+ * must hold qhuff_encode_headers_dyn_bound(in_bytes, n, m) =
+ * qhuff_encode_headers_bound(in_bytes, n, m).  The buffer contract above
+ * applies: out[0 .. sec_out[m]), sec_out[0 .. m] and the optional arrays are
+ * written, nothing else.
+ *
+ * Launches on `stream`, after one clear of the scratch: the index build
+ * (two open-addressing indices over the d entries, by name+value hash and by
+ * name hash, qhuff_dyn_index_slots(d) 32-bit slots each: the smallest power
+ * of two >= 2d, at least 64; rebuilt on every call), the lookup, which writes
+ * every header's two items with its section's Base and reduces each
+ * section's largest reference into a word of scratch, a small launch that
+ * writes every section's two prefix items from that word (all three timed as
+ * QHUFF_KIND_HASH), then qhuff_encode_wire's launch and the gather of
+ * sec_out unchanged.  For n = 0 every section is 00 00.  Scratch belongs to
+ * the context, grown on demand and ordered across streams as
+ * qhuff_encode_headers'.
+ *
+ * qhuff_encode_headers_dyn: device pointers, asynchronous.  QHUFF_EINVAL for
+ * a null pointer, QHUFF_ERANGE when 2n + 2m passes 32 bits, first + d passes
+ * 2^32 - 1 or d passes 2^28.  The form of sec_hdr, sec_win, sec_base and
+ * tab->off is THE CALLER'S DUTY: the kernel clamps a window into [first,
+ * first + d] and a Base to at most first + d, clamps an entry's offsets into
+ * [off[0], off[2d]] and takes a decreasing pair as an empty string, so
+ * nothing outside the arrays and the table's bytes is read, and items stay
+ * inside their arrays.
+ * qhuff_encode_headers_dyn_host: host pointers, synchronous -- one upload of
+ * the headers and the table, the launches, then sec_out, the optional arrays
+ * and exactly sec_out[m] bytes come back; the host's only loops are the
+ * checks of the offsets, the windows and the Bases.  QHUFF_EINVAL for a null
+ * pointer, for the sec_hdr / off faults of qhuff_encode_headers_host, for a
+ * window or a Base outside the rule, for a decreasing tab->off; QHUFF_ERANGE
+ * as there and as above; nothing is written then.
+ *
+ * qhuff_dyn_lookup / _host / _cpu: the lookup alone, as qhuff_static_lookup
+ * is -- the two hashes (each may be NULL), kind, static_id and dyn_id (may be
+ * NULL) per header, one window [win_lo, win_hi) for the whole call, under
+ * the same rule.  A stateful encoder copies the results into its
+ * lsxpack_header and skips its bucket walks.
+ * The index build and the lookup launch, timed as QHUFF_KIND_HASH.  _cpu:
+ * the kernel's lookup source on the host over host pointers, no context and
+ * no device call; it returns what the host form returns.
+ * qhuff_dyn_index_slots(d) (diagnostic, host only): the slots of each index
+ * for a table of d entries; an entry's first slot is hash & (slots - 1), the
+ * name+value hash in one index, the name hash in the other. */
+#define QHUFF_FEATURE_ENCODE_HEADERS_DYN 1
+
+int qhuff_dyn_lookup(qhuff_ctx *ctx, const uint8_t *in, const uint32_t *off,
+                     uint32_t n, const struct qhuff_dyn_table *tab,
+                     uint32_t win_lo, uint32_t win_hi, uint32_t *name_hash,
+                     uint32_t *nameval_hash, uint8_t *kind,
+                     uint8_t *static_id, uint32_t *dyn_id, void *stream);
+
+int qhuff_dyn_lookup_host(qhuff_ctx *ctx, const uint8_t *in,
+                          const uint32_t *off, uint32_t n,
+                          const struct qhuff_dyn_table *tab, uint32_t win_lo,
+                          uint32_t win_hi, uint32_t *name_hash,
+                          uint32_t *nameval_hash, uint8_t *kind,
+                          uint8_t *static_id, uint32_t *dyn_id);
+
+int qhuff_dyn_lookup_cpu(const uint8_t *in, const uint32_t *off, uint32_t n,
+                         const struct qhuff_dyn_table *tab, uint32_t win_lo,
+                         uint32_t win_hi, uint32_t *name_hash,
+                         uint32_t *nameval_hash, uint8_t *kind,
+                         uint8_t *static_id, uint32_t *dyn_id);
+
+uint32_t qhuff_dyn_index_slots(uint32_t d);
+
+uint64_t qhuff_encode_headers_dyn_bound(uint64_t in_bytes, uint32_t n,
+                                        uint32_t m);
+
+int qhuff_encode_headers_dyn(qhuff_ctx *ctx, const uint8_t *in,
+                             const uint32_t *off, uint32_t n,
+                             const uint8_t *hflags, const uint32_t *sec_hdr,
+                             uint32_t m, const struct qhuff_dyn_table *tab,
+                             const uint32_t *sec_win,
+                             const uint32_t *sec_base, uint8_t *out,
+                             uint32_t *sec_out, uint8_t *kind,
+                             uint8_t *static_id, uint32_t *dyn_id,
+                             void *stream);
+
+int qhuff_encode_headers_dyn_host(qhuff_ctx *ctx, const uint8_t *in,
+                                  const uint32_t *off, uint32_t n,
+                                  const uint8_t *hflags,
+                                  const uint32_t *sec_hdr, uint32_t m,
+                                  const struct qhuff_dyn_table *tab,
+                                  const uint32_t *sec_win,
+                                  const uint32_t *sec_base, uint8_t *out,
+                                  uint32_t *sec_out, uint8_t *kind,
+                                  uint8_t *static_id, uint32_t *dyn_id);
+
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman
  * payload was precomputed by a QHUFF_ENC_PAYLOAD batch (huff, huff_len =

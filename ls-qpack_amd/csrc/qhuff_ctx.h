@@ -127,6 +127,15 @@ struct qhuff_ctx
     hipEvent_t hdr_ev;
     hipStream_t hdr_stream;
     bool hdr_have;
+    // the dynamic lookup's scratch (qhuff_dyn_lookup,
+    // qhuff_encode_headers_dyn): dyn_cap words -- a word a section, then the
+    // table's two indices -- rebuilt on every call; ordered across streams
+    // with hdr_ws, by hdr_ev
+    uint32_t *dyn_ws;
+    uint64_t dyn_cap;
+    uint32_t dyn_grid[2];                // resident workgroups of its lookup
+                                         // kernel ([1]: the encode form's),
+                                         // found at the first call
     char err_msg[256];
 };
 

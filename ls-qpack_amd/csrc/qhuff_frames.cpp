@@ -17,8 +17,11 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <new>
+
 #include "../../include/qhuff.h"
 #include "qhuff_lookup_impl.h"
+#include "qhuff_lookup_dyn_impl.h"
 #include "qhuff_names.h"
 #include "qhuff_scan_impl.h"
 
@@ -485,6 +488,94 @@ qhuff_static_lookup_cpu(const uint8_t *in, const uint32_t *off, uint32_t n,
         static_id[i] = (uint8_t) hit.id;
     }
     return QHUFF_OK;
+}
+
+// ---- ... and the dynamic lookup's (qhuff_lookup_dyn_impl.h) -------------------
+
+extern "C" uint32_t
+qhuff_dyn_index_slots(uint32_t d)
+{
+    return qhuff::dyn_index_slots(d);
+}
+
+// the index built entry by entry in ordinal order, then the kernel's lookup
+// source header by header, the window clamped as the kernel clamps it
+static int
+dyn_lookup_cpu_run(const uint8_t *in, const uint32_t *off, uint32_t n,
+                   const struct qhuff_dyn_table *tab, uint32_t win_lo,
+                   uint32_t win_hi, uint32_t *name_hash,
+                   uint32_t *nameval_hash, uint8_t *kind, uint8_t *static_id,
+                   uint32_t *dyn_id)
+{
+    const uint32_t d = tab->d;
+    const uint32_t slots = d ? qhuff::dyn_index_slots(d) : 0;
+    uint32_t *idx = slots ? new (std::nothrow) uint32_t[2ull * slots]() : nullptr;
+    if (slots && !idx)
+        return QHUFF_ENOMEM;
+    qhuff::DynTab<qhuff::HashMem, const uint32_t *> t;
+    t.tb = qhuff::HashMem{tab->bytes};
+    t.off = tab->off;
+    t.nv = idx;
+    t.nm = idx + slots;
+    t.mask = slots ? slots - 1 : 0;
+    t.d = d;
+    t.first = tab->first;
+    t.t0 = d ? tab->off[0] : 0;
+    t.t1 = d ? tab->off[2ull * d] : 0;
+    auto claim = [](uint32_t *p, uint32_t v) {
+        if (*p)
+            return false;
+        *p = v;
+        return true;
+    };
+    for (uint32_t k = 0; k < d; ++k)
+        qhuff::dyn_index_insert(t.tb, t.off, k, t.t0, t.t1, idx, idx + slots,
+                                t.mask, claim);
+    const qhuff::DynRange w = qhuff::dyn_window(win_lo, win_hi, tab->first, d,
+                                                tab->max_entries);
+    const qhuff::HashMem r{in};
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const uint32_t a = off[2ull * i], m = off[2ull * i + 1],
+                       b = off[2ull * i + 2];
+        const uint32_t h1 = qhuff::xxh32(r, a, m - a, QHUFF_XXH_SEED);
+        const uint32_t h2 = qhuff::xxh32(r, m, b - m, h1);
+        const qhuff::DynHit hit = qhuff::dyn_lookup(r, a, m, b, h1, h2,
+                                                    kStaticHost, t, w.lo,
+                                                    w.hi);
+        if (name_hash)
+            name_hash[i] = h1;
+        if (nameval_hash)
+            nameval_hash[i] = h2;
+        kind[i] = (uint8_t) hit.kind;
+        static_id[i] = (uint8_t) hit.id;
+        if (dyn_id)
+            dyn_id[i] = hit.dyn;
+    }
+    delete[] idx;
+    return QHUFF_OK;
+}
+
+// qhuff_dyn_lookup in plain C++, after the host form's checks
+extern "C" int
+qhuff_dyn_lookup_cpu(const uint8_t *in, const uint32_t *off, uint32_t n,
+                     const struct qhuff_dyn_table *tab, uint32_t win_lo,
+                     uint32_t win_hi, uint32_t *name_hash,
+                     uint32_t *nameval_hash, uint8_t *kind,
+                     uint8_t *static_id, uint32_t *dyn_id)
+{
+    if (!off || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    const uint32_t win[2] = {win_lo, win_hi};
+    if (const int rc = qhuff::dyn_enc_check(tab, win, nullptr, 1))
+        return rc;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    for (uint64_t i = 0; i < 2ull * n; ++i)
+        if (off[i + 1] < off[i])
+            return QHUFF_EINVAL;
+    return dyn_lookup_cpu_run(in, off, n, tab, win_lo, win_hi, name_hash,
+                              nameval_hash, kind, static_id, dyn_id);
 }
 
 extern "C" int

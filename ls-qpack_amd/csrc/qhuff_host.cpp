@@ -2,6 +2,7 @@
 // (tables uploaded once, look-back workspace, error word, grid sizing),
 // device-pointer batch calls and host-only helpers (the rest: qhuff_ctx.h).
 #include "qhuff_ctx.h"
+#include "qhuff_lookup_dyn_impl.h"
 
 // ---------------------------------------------------------------------------
 // host side: context, C-ABI
@@ -405,6 +406,8 @@ qhuff_close(qhuff_ctx *c)
         (void) hipFree(c->hdr_ws);
     if (c->hdr_ev)
         (void) hipEventDestroy(c->hdr_ev);
+    if (c->dyn_ws)
+        (void) hipFree(c->dyn_ws);
     if (c->tev)
     {
         for (unsigned i = 0; i < 2 * QHUFF_TIMING_SLOTS; ++i)
@@ -1544,6 +1547,199 @@ qhuff_encode_headers(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
     c->hdr_stream = st;
     c->hdr_have = true;
     r = qhuff_encode_wire(c, in, a.str_off, a.items, (uint32_t) items, out,
+                          item_off, st);
+    if (r)
+        return r;
+    HIPCHK(c, launch_secout(item_off, sec_hdr, m, n, sec_out, st));
+    return QHUFF_OK;
+}
+
+// ---- ... and among the dynamic table's entries (qhuff_lookup_dyn.hip) --------
+
+extern "C" uint64_t
+qhuff_encode_headers_dyn_bound(uint64_t in_bytes, uint32_t n, uint32_t m)
+{
+    // (the same items; a prefix's two integers fit an item's 13 bytes)
+    return qhuff_encode_headers_bound(in_bytes, n, m);
+}
+
+// what the device forms can check of a table: a host struct
+static int
+dyn_tab_ok(const struct qhuff_dyn_table *tab)
+{
+    if (!tab || (tab->d && (!tab->off || !tab->bytes)))
+        return QHUFF_EINVAL;
+    if ((uint64_t) tab->first + tab->d > 0xffffffffull || tab->d > kDynMaxD)
+        return QHUFF_ERANGE;
+    return QHUFF_OK;
+}
+
+// The dynamic lookup's scratch for m sections and a table of d entries --
+// [ric: m words | the two indices: qhuff_dyn_index_slots(d) words each, none
+// when d = 0], cleared on st -- and the table's part of the arguments.
+// After hdr_prepare: the scratch is ordered across streams with hdr_ws, by
+// the same event.
+static int
+dyn_prepare(qhuff_ctx *c, const struct qhuff_dyn_table *tab, uint32_t m,
+            hipStream_t st, DynLookupArgs *a)
+{
+    const uint64_t slots = tab->d ? dyn_index_slots(tab->d) : 0;
+    const uint64_t words = (uint64_t) m + 2 * slots;
+    if (words > c->dyn_cap)
+    {
+        if (c->dyn_ws)
+        {
+            // (earlier calls may still use it)
+            if (c->hdr_have)
+                HIPCHK(c, hipStreamSynchronize(c->hdr_stream));
+            HIPCHK(c, hipFree(c->dyn_ws));
+            c->dyn_ws = nullptr;
+            c->dyn_cap = 0;
+        }
+        const uint64_t cap = words < 4096 ? 4096 : words;
+        HIPCHK(c, hipMalloc((void **) &c->dyn_ws, 4 * cap));
+        c->dyn_cap = cap;
+    }
+    if (words)
+        HIPCHK(c, hipMemsetAsync(c->dyn_ws, 0, 4 * words, st));
+    a->tab = tab->d ? tab->bytes : nullptr;
+    a->tab_off = tab->d ? tab->off : nullptr;
+    a->ric = c->dyn_ws;
+    a->nv = slots ? c->dyn_ws + m : nullptr;
+    a->nm = slots ? c->dyn_ws + m + slots : nullptr;
+    a->mask = slots ? (uint32_t) slots - 1 : 0;
+    a->d = tab->d;
+    a->first = tab->first;
+    a->max_entries = tab->max_entries;
+    a->win_lo = tab->first;
+    a->win_hi = tab->first + tab->d;
+    return QHUFF_OK;
+}
+
+// the index build (d != 0) and the lookup, on st
+static int
+dyn_launches(qhuff_ctx *c, const DynLookupArgs &a, hipStream_t st)
+{
+    if (a.d)
+    {
+        const int r = timed(c, QHUFF_KIND_HASH, "launch_dyn_index",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_dyn_index(a, st, e0, e1);
+        });
+        // (a launch went out: later calls on another stream wait for it)
+        c->hdr_stream = st;
+        c->hdr_have = true;
+        if (r)
+            return r;
+    }
+    const bool enc = a.l.items != nullptr;
+    if (!c->dyn_grid[enc])
+    {
+        // (the workgroups of this kernel that fit at once, as hash_grid is
+        // the hash kernel's; any grid is correct)
+        int occ = 0;
+        HIPCHK(c, lookup_dyn_occupancy(enc, &occ));
+        c->dyn_grid[enc] = (uint32_t) (occ > 0 ? occ : 1) * (uint32_t) c->n_cu;
+    }
+    const int r = timed(c, QHUFF_KIND_HASH, "launch_lookup_dyn",
+                        [&](hipEvent_t e0, hipEvent_t e1) {
+        return launch_lookup_dyn(a, c->dyn_grid[enc], st, e0, e1);
+    });
+    if (!r)
+    {
+        c->hdr_stream = st;
+        c->hdr_have = true;
+    }
+    return r;
+}
+
+extern "C" int
+qhuff_dyn_lookup(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                 uint32_t n, const struct qhuff_dyn_table *tab,
+                 uint32_t win_lo, uint32_t win_hi, uint32_t *name_hash,
+                 uint32_t *nameval_hash, uint8_t *kind, uint8_t *static_id,
+                 uint32_t *dyn_id, void *stream)
+{
+    if (!c || !off || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    if (const int r = dyn_tab_ok(tab))
+        return r;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0)
+        return QHUFF_OK;
+    if (const int r = hdr_prepare(c, 0, st))
+        return r;
+    DynLookupArgs a = {};
+    a.l = lookup_args(in, off, n, name_hash, nameval_hash, kind, static_id);
+    a.dyn_id = dyn_id;
+    if (const int r = dyn_prepare(c, tab, 0, st, &a))
+        return r;
+    a.win_lo = win_lo;
+    a.win_hi = win_hi;
+    return dyn_launches(c, a, st);
+}
+
+extern "C" int
+qhuff_encode_headers_dyn(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                         uint32_t n, const uint8_t *hflags,
+                         const uint32_t *sec_hdr, uint32_t m,
+                         const struct qhuff_dyn_table *tab,
+                         const uint32_t *sec_win, const uint32_t *sec_base,
+                         uint8_t *out, uint32_t *sec_out, uint8_t *kind,
+                         uint8_t *static_id, uint32_t *dyn_id, void *stream)
+{
+    if (!c || !off || !sec_hdr || !sec_out || (n && !in) || ((n || m) && !out))
+        return QHUFF_EINVAL;
+    if (const int r = dyn_tab_ok(tab))
+        return r;
+    const uint64_t items = 2ull * n + 2ull * m;
+    if (items > 0xffffffffull)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (items == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(sec_out, 0, 4, st));
+        return QHUFF_OK;
+    }
+    // (headers without a section: sec_hdr[0] = 0 != n, the caller's breach)
+    if (m == 0)
+        return QHUFF_EINVAL;
+    if (n == 0)
+    {
+        // (no header, no reference: every section is 00 00)
+        HIPCHK(c, launch_empty_sections(m, out, sec_out, st));
+        return QHUFF_OK;
+    }
+    if (const int r = hdr_prepare(c, items, st))
+        return r;
+    DynLookupArgs a = {};
+    a.l = lookup_args(in, off, n, nullptr, nullptr, kind, static_id);
+    a.l.hflags = hflags;
+    a.l.sec_hdr = sec_hdr;
+    a.l.m = m;
+    a.l.items = (struct qhuff_item *) c->hdr_ws;
+    a.l.str_off = (uint32_t *) (c->hdr_ws + 8 * c->hdr_cap);
+    uint32_t *item_off = (uint32_t *) (c->hdr_ws + 8 * c->hdr_cap
+                                       + hdr_up16(4 * (c->hdr_cap + 1)));
+    a.sec_win = sec_win;
+    a.sec_base = sec_base;
+    a.dyn_id = dyn_id;
+    if (const int r = dyn_prepare(c, tab, m, st, &a))
+        return r;
+    int r = dyn_launches(c, a, st);
+    if (r)
+        return r;
+    r = timed(c, QHUFF_KIND_HASH, "launch_dyn_prefix",
+              [&](hipEvent_t e0, hipEvent_t e1) {
+        return launch_dyn_prefix(a, st, e0, e1);
+    });
+    if (r)
+        return r;
+    r = qhuff_encode_wire(c, in, a.l.str_off, a.l.items, (uint32_t) items, out,
                           item_off, st);
     if (r)
         return r;

@@ -2,6 +2,7 @@
 // registration and the per-string mirrors of the reference entry points.
 #include "qhuff_ctx.h"
 #include "qhuff_scan_impl.h"
+#include "qhuff_lookup_dyn_impl.h"
 
 namespace qhuff {
 // qhuff_frames.cpp: a VALUE literal's static-table name length, or 0
@@ -1717,6 +1718,181 @@ qhuff_encode_headers_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
         memcpy(kind, c->h_stage + o_k, n);
     if (static_id && n)
         memcpy(static_id, c->h_stage + o_id, n);
+    return QHUFF_OK;
+}
+
+// ---- ... and among the dynamic table's entries, host buffers -------------------
+
+// the table's part of a stage: its bytes (rebased by -off[0]) and its offsets
+struct DynUp
+{
+    uint64_t t0, tb;                     // off[0], the bytes held
+    size_t bytes, off;                   // where they lie in the stage
+};
+
+static DynUp
+dyn_up(const struct qhuff_dyn_table *tab, size_t at)
+{
+    DynUp u;
+    const uint64_t d = tab->d;
+    u.t0 = d ? tab->off[0] : 0;
+    u.tb = d ? tab->off[2 * d] - u.t0 : 0;
+    u.bytes = at;
+    u.off = at + up16(u.tb) + 16;
+    return u;
+}
+
+static size_t
+dyn_up_end(const struct qhuff_dyn_table *tab, const DynUp &u)
+{
+    return u.off + up16(tab->d ? 4 * (2ull * tab->d + 1) : 0);
+}
+
+// Stage layout: [name/value bytes | offsets (2n + 1) | table bytes | table
+// off | name_hash | nameval_hash | dyn_id | kind | static_id]; `in` and the
+// table's bytes are passed rebased by -off[0].
+extern "C" int
+qhuff_dyn_lookup_host(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                      uint32_t n, const struct qhuff_dyn_table *tab,
+                      uint32_t win_lo, uint32_t win_hi, uint32_t *name_hash,
+                      uint32_t *nameval_hash, uint8_t *kind,
+                      uint8_t *static_id, uint32_t *dyn_id)
+{
+    if (!c || !off || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    const uint32_t win[2] = {win_lo, win_hi};
+    if (const int rc = dyn_enc_check(tab, win, nullptr, 1))
+        return rc;
+    if (const int rc = headers_ok(off, n))
+        return rc;
+    if (n == 0)
+        return QHUFF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
+    const size_t o_off = up16(bytes) + 16;
+    const DynUp u = dyn_up(tab, o_off + up16(4ull * (2ull * n + 1)));
+    const size_t o_h1 = dyn_up_end(tab, u);
+    const size_t o_h2 = o_h1 + up16(4ull * n), o_did = o_h2 + up16(4ull * n);
+    const size_t o_k = o_did + up16(4ull * n);
+    const size_t o_id = o_k + up16(n), total = o_id + up16(n);
+    int rc = stage_up(c, total,
+                      {{bytes ? in + a0 : nullptr, bytes, 0},
+                       {off, 4ull * (2ull * n + 1), o_off},
+                       {u.tb ? tab->bytes + u.t0 : nullptr, u.tb, u.bytes},
+                       {tab->off, tab->d ? 4 * (2ull * tab->d + 1) : 0, u.off}},
+                      o_h1);
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t st = c->own_stream;
+    struct qhuff_dyn_table dev = *tab;
+    dev.bytes = D + u.bytes - u.t0;
+    dev.off = tab->d ? (const uint32_t *) (D + u.off) : nullptr;
+    rc = qhuff_dyn_lookup(c, D - a0, (const uint32_t *) (D + o_off), n, &dev,
+                          win_lo, win_hi, (uint32_t *) (D + o_h1),
+                          (uint32_t *) (D + o_h2), D + o_k, D + o_id,
+                          (uint32_t *) (D + o_did), st);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(H + o_h1, D + o_h1, total - o_h1,
+                             hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (name_hash)
+        memcpy(name_hash, H + o_h1, 4ull * n);
+    if (nameval_hash)
+        memcpy(nameval_hash, H + o_h2, 4ull * n);
+    if (dyn_id)
+        memcpy(dyn_id, H + o_did, 4ull * n);
+    memcpy(kind, H + o_k, n);
+    memcpy(static_id, H + o_id, n);
+    return QHUFF_OK;
+}
+
+// Header lists to field sections against the table
+// (qhuff_encode_headers_dyn), as qhuff_encode_headers_host: one upload of the
+// headers and the table, the launches, then sec_out, the optional arrays and
+// exactly sec_out[m] bytes come back.  The host loops over the offsets, the
+// sections' bounds, the windows and the Bases only to check them.  Stage
+// layout: [bytes | off | hflags | sec_hdr | table bytes | table off | sec_win
+// | sec_base | sec_out | dyn_id | kind | static_id | out].
+extern "C" int
+qhuff_encode_headers_dyn_host(qhuff_ctx *c, const uint8_t *in,
+                              const uint32_t *off, uint32_t n,
+                              const uint8_t *hflags, const uint32_t *sec_hdr,
+                              uint32_t m, const struct qhuff_dyn_table *tab,
+                              const uint32_t *sec_win,
+                              const uint32_t *sec_base, uint8_t *out,
+                              uint32_t *sec_out, uint8_t *kind,
+                              uint8_t *static_id, uint32_t *dyn_id)
+{
+    if (!c || !off || !sec_hdr || !sec_out || (n && !in) || ((n || m) && !out))
+        return QHUFF_EINVAL;
+    if (2ull * n + 2ull * m > 0xffffffffull)
+        return QHUFF_ERANGE;
+    if (sec_hdr[0] != 0 || sec_hdr[m] != n)
+        return QHUFF_EINVAL;
+    for (uint32_t s = 0; s < m; ++s)
+        if (sec_hdr[s + 1] < sec_hdr[s])
+            return QHUFF_EINVAL;
+    if (const int rc = headers_ok(off, n))
+        return rc;
+    if (const int rc = dyn_enc_check(tab, sec_win, sec_base, m))
+        return rc;
+    if (m == 0)
+    {
+        sec_out[0] = 0;
+        return QHUFF_OK;
+    }
+    const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
+    const uint64_t bound = qhuff_encode_headers_dyn_bound(bytes, n, m);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t o_off = up16(bytes) + 16;
+    const size_t o_fl = o_off + up16(4ull * (2ull * n + 1));
+    const size_t o_sh = o_fl + up16(n);
+    const DynUp u = dyn_up(tab, o_sh + up16(4ull * (m + 1ull)));
+    const size_t o_sw = dyn_up_end(tab, u);
+    const size_t o_sb = o_sw + up16(sec_win ? 8ull * m : 0);
+    const size_t o_so = o_sb + up16(sec_base ? 4ull * m : 0);
+    const size_t o_did = o_so + up16(4ull * (m + 1ull));
+    const size_t o_k = o_did + up16(4ull * n);
+    const size_t o_id = o_k + up16(n), o_out = o_id + up16(n);
+    int rc = stage_up(c, o_out + up16(bound),
+                      {{bytes ? in + a0 : nullptr, bytes, 0},
+                       {off, 4ull * (2ull * n + 1), o_off},
+                       {hflags, hflags ? (size_t) n : 0, o_fl},
+                       {sec_hdr, 4ull * (m + 1ull), o_sh},
+                       {u.tb ? tab->bytes + u.t0 : nullptr, u.tb, u.bytes},
+                       {tab->off, tab->d ? 4 * (2ull * tab->d + 1) : 0, u.off},
+                       {sec_win, sec_win ? 8ull * m : 0, o_sw},
+                       {sec_base, sec_base ? 4ull * m : 0, o_sb}}, o_so);
+    if (rc)
+        return rc;
+    uint8_t *D = c->d_stage;
+    struct qhuff_dyn_table dev = *tab;
+    dev.bytes = D + u.bytes - u.t0;
+    dev.off = tab->d ? (const uint32_t *) (D + u.off) : nullptr;
+    rc = qhuff_encode_headers_dyn(c, D - a0, (const uint32_t *) (D + o_off), n,
+                                  hflags ? D + o_fl : nullptr,
+                                  (const uint32_t *) (D + o_sh), m, &dev,
+                                  sec_win ? (const uint32_t *) (D + o_sw)
+                                          : nullptr,
+                                  sec_base ? (const uint32_t *) (D + o_sb)
+                                           : nullptr,
+                                  D + o_out, (uint32_t *) (D + o_so), D + o_k,
+                                  D + o_id, (uint32_t *) (D + o_did),
+                                  c->own_stream);
+    if (rc)
+        return rc;
+    if ((rc = stage_down(c, o_so, o_so, o_out, m, out, sec_out)))
+        return rc;
+    if (kind && n)
+        memcpy(kind, c->h_stage + o_k, n);
+    if (static_id && n)
+        memcpy(static_id, c->h_stage + o_id, n);
+    if (dyn_id && n)
+        memcpy(dyn_id, c->h_stage + o_did, 4ull * n);
     return QHUFF_OK;
 }
 

@@ -156,6 +156,28 @@ struct LookupArgs
     uint32_t m;
 };
 
+// headers looked up in the static table and among the dynamic table's
+// entries (qhuff_lookup_dyn.hip): the lookup's arguments, the table, its two
+// indices (mask + 1 slots each, the context's scratch, cleared on the stream
+// before the index launch; null when d = 0) and the window.  Lookup form
+// (l.items = null): every header sees [win_lo, win_hi).  Encode form:
+// section s sees sec_win[2s .. 2s + 1] (null: [win_lo, win_hi)) with the Base
+// sec_base[s] (null: its window's end); ric holds a word a section, cleared
+// on the stream before the lookup launch.
+struct DynLookupArgs
+{
+    LookupArgs l;
+    const uint8_t *tab;          // the table's bytes, or null when d = 0
+    const uint32_t *tab_off;     // 2d + 1, or null when d = 0
+    uint32_t *nv, *nm;           // by name+value hash, by name hash
+    const uint32_t *sec_win;     // 2m, or null
+    const uint32_t *sec_base;    // m, or null
+    uint32_t *dyn_id;            // n, or null
+    uint32_t *ric;               // m: 1 + the largest index a section named
+    uint32_t d, first, max_entries, mask;
+    uint32_t win_lo, win_hi;
+};
+
 // ---- low-latency service (qhuff_service.hip, qhuff_svc_host.cpp) ----------
 //
 // One request slot per service wave, in pinned host memory mapped into the
@@ -311,6 +333,20 @@ hipError_t hash_occupancy(int *blocks_per_cu);
 hipError_t launch_lookup(const LookupArgs &a, uint32_t max_grid,
                          hipStream_t st, hipEvent_t ev0 = nullptr,
                          hipEvent_t ev1 = nullptr);
+// the three launches of a lookup against the dynamic table
+// (qhuff_lookup_dyn.hip): the index build (a.d != 0), the lookup (a.l.n != 0)
+// and, in the encode form, the sections' prefix items (a.l.m != 0)
+hipError_t launch_dyn_index(const DynLookupArgs &a, hipStream_t st,
+                            hipEvent_t ev0 = nullptr,
+                            hipEvent_t ev1 = nullptr);
+hipError_t launch_lookup_dyn(const DynLookupArgs &a, uint32_t max_grid,
+                             hipStream_t st, hipEvent_t ev0 = nullptr,
+                             hipEvent_t ev1 = nullptr);
+hipError_t launch_dyn_prefix(const DynLookupArgs &a, hipStream_t st,
+                             hipEvent_t ev0 = nullptr,
+                             hipEvent_t ev1 = nullptr);
+// (enc: of the encode form's kernel, else of the lookup form's)
+hipError_t lookup_dyn_occupancy(bool enc, int *blocks_per_cu);
 // m sections of no headers: out = m x "00 00", sec_out[s] = 2s, s in [0, m]
 hipError_t launch_empty_sections(uint32_t m, uint8_t *out, uint32_t *sec_out,
                                  hipStream_t st);

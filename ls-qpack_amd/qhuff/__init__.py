@@ -61,6 +61,9 @@ EXPORTS = (
     "qhuff_scan_headers_dyn", "qhuff_scan_headers_dyn_host",
     "qhuff_scan_headers_dyn_cpu", "qhuff_decode_headers_dyn_bound",
     "qhuff_decode_headers_dyn", "qhuff_decode_headers_dyn_host",
+    "qhuff_dyn_lookup", "qhuff_dyn_lookup_host", "qhuff_dyn_lookup_cpu",
+    "qhuff_dyn_index_slots", "qhuff_encode_headers_dyn_bound",
+    "qhuff_encode_headers_dyn", "qhuff_encode_headers_dyn_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -404,6 +407,31 @@ def lib():
                                                     C.c_uint32, vp, vp, vp,
                                                     vp, vp, vp, vp, vp, vp,
                                                     vp, vp]
+        L.qhuff_dyn_lookup.restype = C.c_int
+        L.qhuff_dyn_lookup.argtypes = [vp, vp, vp, C.c_uint32, dtp, C.c_uint32,
+                                       C.c_uint32, vp, vp, vp, vp, vp, vp]
+        L.qhuff_dyn_lookup_host.restype = C.c_int
+        L.qhuff_dyn_lookup_host.argtypes = [vp, vp, vp, C.c_uint32, dtp,
+                                            C.c_uint32, C.c_uint32, vp, vp,
+                                            vp, vp, vp]
+        L.qhuff_dyn_lookup_cpu.restype = C.c_int
+        L.qhuff_dyn_lookup_cpu.argtypes = [vp, vp, C.c_uint32, dtp,
+                                           C.c_uint32, C.c_uint32, vp, vp, vp,
+                                           vp, vp]
+        L.qhuff_dyn_index_slots.restype = C.c_uint32
+        L.qhuff_dyn_index_slots.argtypes = [C.c_uint32]
+        L.qhuff_encode_headers_dyn_bound.restype = C.c_uint64
+        L.qhuff_encode_headers_dyn_bound.argtypes = [C.c_uint64, C.c_uint32,
+                                                     C.c_uint32]
+        L.qhuff_encode_headers_dyn.restype = C.c_int
+        L.qhuff_encode_headers_dyn.argtypes = [vp, vp, vp, C.c_uint32, vp, vp,
+                                               C.c_uint32, dtp, vp, vp, vp,
+                                               vp, vp, vp, vp, vp]
+        L.qhuff_encode_headers_dyn_host.restype = C.c_int
+        L.qhuff_encode_headers_dyn_host.argtypes = [vp, vp, vp, C.c_uint32,
+                                                    vp, vp, C.c_uint32, dtp,
+                                                    vp, vp, vp, vp, vp, vp,
+                                                    vp]
         L.qhuff_decode_headers_host.restype = C.c_int
         L.qhuff_decode_headers_host.argtypes = [vp, vp, u32p, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, u32p,
@@ -743,6 +771,47 @@ def static_lookup_cpu(data, off):
     if rc != OK:
         raise QhuffError("qhuff_static_lookup_cpu failed: %d" % rc)
     return h1[:n], h2[:n], kind[:n], sid[:n]
+
+
+def encode_headers_dyn_bound(in_bytes, n, m):
+    return int(lib().qhuff_encode_headers_dyn_bound(in_bytes, n, m))
+
+
+def dyn_index_slots(d):
+    """qhuff_dyn_index_slots: the slots of each of the dynamic lookup's two
+    indices for a table of d entries"""
+    return int(lib().qhuff_dyn_index_slots(d))
+
+
+def _window(table, win):
+    """(lo, hi) of a window, None: the whole table (data, off, first, ...)"""
+    if win is not None:
+        return int(win[0]), int(win[1])
+    off, first = table[1], (table[2] if len(table) > 2 else 0)
+    d = 0 if off is None else (len(off) - 1) // 2
+    return first, first + d
+
+
+def dyn_lookup_cpu(data, off, table, win=None):
+    """qhuff_dyn_lookup_cpu: the dynamic lookup kernel's source run on the
+    host.  table: (data, off, first, max_entries) host arrays as
+    dyn_table_host takes them; win: (lo, hi) or None, the whole table ->
+    (ret, name_hash, nameval_hash uint32 [n], kind, static_id uint8 [n],
+    dyn_id uint32 [n])."""
+    import numpy as np
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint32)
+    n = (len(off) - 1) // 2
+    h1, h2, did = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+    kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+    t, keep = dyn_table_host(*table)
+    lo, hi = _window(table, win)
+    ret = lib().qhuff_dyn_lookup_cpu(
+        _np_ptr(data) if len(data) else _np_ptr(np.zeros(1, np.uint8)),
+        _np_ptr(off), n, C.byref(t), lo, hi, _np_ptr(h1), _np_ptr(h2),
+        _np_ptr(kind), _np_ptr(sid), _np_ptr(did))
+    del keep
+    return ret, h1[:n], h2[:n], kind[:n], sid[:n], did[:n]
 
 
 def dec_int(buf, prefix_bits):
@@ -1236,6 +1305,125 @@ class Codec:
             _np_ptr(kind), _np_ptr(sid))
         self._check(rc, "qhuff_encode_headers_host")
         return out[:sec_out[-1]], sec_out, kind[:n], sid[:n]
+
+    # ... and among the dynamic table's entries ----------------------------------
+    def dyn_lookup(self, data, off, tab_data, tab_off, first, max_entries,
+                   win=None, stream=None):
+        """qhuff_dyn_lookup on device tensors: data / off as static_lookup,
+        tab_data uint8 / tab_off int32 [2d+1] cuda tensors (None, None: d =
+        0); win (lo, hi) or None, the whole table -> (name_hash, nameval_hash
+        int32 [n] (uint32 bits), kind, static_id uint8 [n], dyn_id int32 [n]
+        (uint32 bits))."""
+        import torch
+        n = (off.numel() - 1) // 2
+        d = (tab_off.numel() - 1) // 2 if tab_off is not None else 0
+        h1, h2, did = (torch.empty(max(n, 1), dtype=torch.int32,
+                                   device=data.device) for _ in range(3))
+        kind, sid = (torch.empty(max(n, 1), dtype=torch.uint8,
+                                 device=data.device) for _ in range(2))
+        t = DynTable(tab_data.data_ptr() if d else None,
+                     tab_off.data_ptr() if d else None, d, first, max_entries)
+        lo, hi = win if win is not None else (first, first + d)
+        rc = lib().qhuff_dyn_lookup(
+            self._ctx, data.data_ptr(), off.data_ptr(), n, C.byref(t), lo, hi,
+            h1.data_ptr(), h2.data_ptr(), kind.data_ptr(), sid.data_ptr(),
+            did.data_ptr(), self._stream(stream))
+        self._check(rc, "qhuff_dyn_lookup")
+        return h1[:n], h2[:n], kind[:n], sid[:n], did[:n]
+
+    def dyn_lookup_host(self, data, off, table, win=None):
+        """qhuff_dyn_lookup_host over host buffers; table as dyn_table_host
+        takes it -> (ret, name_hash, nameval_hash, kind, static_id, dyn_id);
+        ret OK, or EINVAL / ERANGE of the argument checks."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = (len(off) - 1) // 2
+        h1, h2, did = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+        t, keep = dyn_table_host(*table)
+        lo, hi = _window(table, win)
+        ret = lib().qhuff_dyn_lookup_host(
+            self._ctx, _np_ptr(data) if len(data) else None, _np_ptr(off), n,
+            C.byref(t), lo, hi, _np_ptr(h1), _np_ptr(h2), _np_ptr(kind),
+            _np_ptr(sid), _np_ptr(did))
+        del keep
+        if ret not in (EINVAL, ERANGE):
+            self._check(ret, "qhuff_dyn_lookup_host")
+        return ret, h1[:n], h2[:n], kind[:n], sid[:n], did[:n]
+
+    def encode_headers_dyn_into(self, data, off, n, hflags, sec_hdr, m, tab,
+                                sec_win, sec_base, out, sec_out, kind=None,
+                                static_id=None, dyn_id=None, stream=None):
+        """qhuff_encode_headers_dyn on device tensors; tab: a DynTable of
+        device pointers; hflags, sec_win, sec_base, kind, static_id and
+        dyn_id may be None.  The form of the arrays is the caller's duty."""
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        rc = lib().qhuff_encode_headers_dyn(
+            self._ctx, data.data_ptr(), off.data_ptr(), n, opt(hflags),
+            sec_hdr.data_ptr(), m, C.byref(tab), opt(sec_win), opt(sec_base),
+            out.data_ptr(), sec_out.data_ptr(), opt(kind), opt(static_id),
+            opt(dyn_id), self._stream(stream))
+        self._check(rc, "qhuff_encode_headers_dyn")
+
+    def encode_headers_dyn(self, data, off, sec_hdr, tab_data, tab_off, first,
+                           max_entries, sec_win=None, sec_base=None,
+                           hflags=None, stream=None):
+        """Device tensors as encode_headers, the table as dyn_lookup, sec_win
+        int32 [2m] / sec_base int32 [m] cuda tensors or None -> (out uint8
+        [bound], sec_out int32 [m+1], kind, static_id uint8 [n], dyn_id int32
+        [n])."""
+        import torch
+        n, m = (off.numel() - 1) // 2, sec_hdr.numel() - 1
+        d = (tab_off.numel() - 1) // 2 if tab_off is not None else 0
+        out = torch.empty(encode_headers_dyn_bound(int(data.numel()), n, m),
+                          dtype=torch.uint8, device=data.device)
+        sec_out = torch.empty(m + 1, dtype=torch.int32, device=data.device)
+        kind, sid = (torch.empty(max(n, 1), dtype=torch.uint8,
+                                 device=data.device) for _ in range(2))
+        did = torch.empty(max(n, 1), dtype=torch.int32, device=data.device)
+        t = DynTable(tab_data.data_ptr() if d else None,
+                     tab_off.data_ptr() if d else None, d, first, max_entries)
+        self.encode_headers_dyn_into(data, off, n, hflags, sec_hdr, m, t,
+                                     sec_win, sec_base, out, sec_out, kind,
+                                     sid, did, stream)
+        return out, sec_out, kind[:n], sid[:n], did[:n]
+
+    def encode_headers_dyn_host(self, data, off, sec_hdr, table, sec_win=None,
+                                sec_base=None, hflags=None):
+        """qhuff_encode_headers_dyn_host over host buffers; table as
+        dyn_table_host takes it, sec_win uint32 [2m] / sec_base uint32 [m] or
+        None -> (ret, out uint8 [sec_out[m]], sec_out uint32 [m+1], kind,
+        static_id uint8 [n], dyn_id uint32 [n]); ret OK, or EINVAL / ERANGE
+        of the argument checks (the arrays then as they were made)."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        sec_hdr = np.ascontiguousarray(sec_hdr, dtype=np.uint32)
+        if hflags is not None:
+            hflags = np.ascontiguousarray(hflags, dtype=np.uint8)
+        n, m = (len(off) - 1) // 2, len(sec_hdr) - 1
+        span = max(int(off[-1]) - int(off[0]), 0)
+        out = np.zeros(encode_headers_dyn_bound(span, n, m), dtype=np.uint8)
+        sec_out = np.zeros(m + 1, dtype=np.uint32)
+        kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+        did = np.zeros(max(n, 1), dtype=np.uint32)
+        t, keep = dyn_table_host(*table)
+        win = _sec_win_host(sec_win)
+        base = None if sec_base is None else \
+            np.ascontiguousarray(sec_base, dtype=np.uint32)
+        ret = lib().qhuff_encode_headers_dyn_host(
+            self._ctx, _np_ptr(data) if len(data) else None, _np_ptr(off), n,
+            _np_ptr(hflags) if hflags is not None and n else None,
+            _np_ptr(sec_hdr), m, C.byref(t),
+            _np_ptr(win) if win is not None and m else None,
+            _np_ptr(base) if base is not None and m else None, _np_ptr(out),
+            _np_ptr(sec_out), _np_ptr(kind), _np_ptr(sid), _np_ptr(did))
+        del keep
+        if ret in (EINVAL, ERANGE):
+            return ret, out[:0], sec_out, kind[:n], sid[:n], did[:n]
+        self._check(ret, "qhuff_encode_headers_dyn_host")
+        return ret, out[:sec_out[-1]], sec_out, kind[:n], sid[:n], did[:n]
 
     # field sections decoded to header lists --------------------------------
     def scan_headers_into(self, buf, sec_off, m, strs, max_hdrs, hdr_off, rc,
