@@ -1290,6 +1290,177 @@ int qhuff_encode_headers_dyn_host(qhuff_ctx *ctx, const uint8_t *in,
                                   uint32_t *sec_out, uint8_t *kind,
                                   uint8_t *static_id, uint32_t *dyn_id);
 
+/* ---- the _dyn calls over many connections: a dynamic table per section -----
+ * One struct qhuff_dyn_table is one QPACK connection; sec_win only lets the
+ * sections of a batch see different moments of that one history.  These calls
+ * take a set of T tables and, per section, the table it belongs to, so that
+ * one batch holds sections of many connections.
+ * QHUFF_FEATURE_HEADERS_TABS and the symbols announce it (the ABI version is
+ * unchanged); the calls above behave as before, and a batch with T = 1 and
+ * sec_tab all 0 gives through these calls exactly what it gives through them.
+ *
+ * struct qhuff_dyn_tables is a read-only view of T tables that share one
+ * arena: `bytes` and `off` as in struct qhuff_dyn_table over all D = ent[T]
+ * entries, table c's entries being the ordinals [ent[c], ent[c + 1]), oldest
+ * first, entry ent[c] + k with the absolute index first[c] + k of that table;
+ * max_entries[c] is its MaxEntries.  A table may be empty.  T = 0 with null
+ * pointers is legal: every section then behaves as one of a table with d = 0
+ * and max_entries = 0, and sec_tab may be NULL.
+ *
+ * Every call takes `tabs, sec_tab` where its _dyn counterpart takes `tab`:
+ * sec_tab[s] (m entries) is the table of section s.  Everything else means
+ * what it means there, read against table sec_tab[s]: sec_win[2s .. 2s + 1],
+ * sec_base[s] and dyn_id[] are absolute indices of that table (a NULL sec_win:
+ * the whole of that table); a DYN descriptor's instr is a byte offset in the
+ * shared `bytes`.  The rules per section -- rc[s] (qhuff_scan_headers_dyn,
+ * 1.-5.), the choice of the line and the prefix (qhuff_encode_headers_dyn,
+ * 1.-5. and "The section's prefix") -- are those stated above, applied to
+ * (tabs, sec_tab[s]); they are not restated here.
+ *
+ * qhuff_scan_headers_tabs / _host / _cpu: qhuff_scan_headers_dyn's three.
+ * qhuff_decode_headers_tabs_host: the whole decode path in one call -- this
+ * scan, then qhuff_decode_headers_dyn's launch unchanged on the shared bytes
+ * (the descriptors already address them); `out` holds
+ * qhuff_decode_headers_dyn_bound(wire bytes, max_hdrs, the longest entry of
+ * all tables).
+ * qhuff_dyn_lookup_tabs / _host / _cpu: the lookup alone, by sections: header
+ * j of section s (sec_hdr[s] <= j < sec_hdr[s + 1]; sec_hdr as in
+ * qhuff_encode_headers) is looked up in table sec_tab[s] within sec_win[2s ..
+ * 2s + 1], under the encode calls' window rule.  _cpu: the kernel's lookup
+ * source on the host.
+ * qhuff_encode_headers_tabs / _host: qhuff_encode_headers_dyn's two; the
+ * bound is qhuff_encode_headers_bound.  Launches: the index build -- ONE pair
+ * of open-addressing indices over all D entries,
+ * qhuff_dyn_tables_index_slots(D) slots each (the smallest power of two >= 2D,
+ * at least 64), a slot holding a global ordinal + 1, an entry's first slot
+ * (hash ^ mix(c)) & (slots - 1) with c its table: connections hold the same
+ * popular headers, and without the table in the slot an entry held by every
+ * one of T tables would make one probe run of length T --, the lookup, the
+ * prefix launch with max_entries[sec_tab[s]], then qhuff_encode_wire's launch
+ * and the gather of sec_out unchanged.
+ *
+ * Host and _cpu forms: QHUFF_EINVAL for a null pointer, ent[0] != 0 or a
+ * decreasing ent, sec_tab[s] >= T, a decreasing off, a window or a Base
+ * outside its table's rule (and for what the _dyn forms return it for);
+ * QHUFF_ERANGE when first[c] + d_c passes 2^32 - 1, when D passes 2^28, and
+ * for the _dyn forms' 32-bit bounds; nothing is written then.  The host's
+ * only loops are these checks.
+ * Device forms: tabs is a host struct of device pointers; the form of the
+ * arrays is THE CALLER'S DUTY.  The kernels clamp sec_tab[s] to T - 1, ent
+ * values to D (a decreasing pair is an empty table), windows and Bases into
+ * their table and an entry's offsets as the _dyn kernels do, so nothing
+ * outside the arrays is read or written.  The scan's kernels read D = ent[T]
+ * on the device (so tabs->off may be NULL there only when T = 0:
+ * QHUFF_EINVAL otherwise).  The lookup and encode forms size their indices
+ * by D on the host: they read ent[T] back with one 4-byte copy on `stream` and wait for
+ * it (the host forms, which know D, do not), then are asynchronous;
+ * QHUFF_ERANGE when that D passes 2^28. */
+#define QHUFF_FEATURE_HEADERS_TABS 1
+
+struct qhuff_dyn_tables {          /* read-only view of T tables          */
+    const uint8_t  *bytes;         /* every table's entries, packed        */
+    const uint32_t *off;           /* off[2D + 1], D = ent[T]              */
+    const uint32_t *ent;           /* ent[T + 1], ent[0] = 0: table c holds
+                                      entry ordinals [ent[c], ent[c + 1]),
+                                      oldest first                         */
+    const uint32_t *first;         /* first[T]: absolute index of table c's
+                                      entry ent[c]                         */
+    const uint32_t *max_entries;   /* max_entries[T]                       */
+    uint32_t T;
+};
+
+int qhuff_scan_headers_tabs(qhuff_ctx *ctx, const uint8_t *buf,
+                            const uint32_t *sec_off, uint32_t m,
+                            const struct qhuff_dyn_tables *tabs,
+                            const uint32_t *sec_tab, const uint32_t *sec_win,
+                            struct qhuff_hstr *strs, uint32_t max_hdrs,
+                            uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                            uint8_t *static_id, uint8_t *hflags,
+                            uint32_t *dyn_id, void *stream);
+
+int qhuff_scan_headers_tabs_host(qhuff_ctx *ctx, const uint8_t *buf,
+                                 const uint32_t *sec_off, uint32_t m,
+                                 const struct qhuff_dyn_tables *tabs,
+                                 const uint32_t *sec_tab,
+                                 const uint32_t *sec_win,
+                                 struct qhuff_hstr *strs, uint32_t max_hdrs,
+                                 uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                                 uint8_t *static_id, uint8_t *hflags,
+                                 uint32_t *dyn_id);
+
+int qhuff_scan_headers_tabs_cpu(const uint8_t *buf, const uint32_t *sec_off,
+                                uint32_t m,
+                                const struct qhuff_dyn_tables *tabs,
+                                const uint32_t *sec_tab,
+                                const uint32_t *sec_win,
+                                struct qhuff_hstr *strs, uint32_t max_hdrs,
+                                uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                                uint8_t *static_id, uint8_t *hflags,
+                                uint32_t *dyn_id);
+
+int qhuff_decode_headers_tabs_host(qhuff_ctx *ctx, const uint8_t *buf,
+                                   const uint32_t *sec_off, uint32_t m,
+                                   const struct qhuff_dyn_tables *tabs,
+                                   const uint32_t *sec_tab,
+                                   const uint32_t *sec_win, uint32_t max_len,
+                                   uint32_t max_hdrs, uint32_t *hdr_off,
+                                   int32_t *rc, uint8_t *kind,
+                                   uint8_t *static_id, uint8_t *hflags,
+                                   uint32_t *dyn_id, uint8_t *out,
+                                   uint32_t *off, uint8_t *status,
+                                   uint32_t *name_hash,
+                                   uint32_t *nameval_hash);
+
+int qhuff_dyn_lookup_tabs(qhuff_ctx *ctx, const uint8_t *in,
+                          const uint32_t *off, uint32_t n,
+                          const uint32_t *sec_hdr, uint32_t m,
+                          const struct qhuff_dyn_tables *tabs,
+                          const uint32_t *sec_tab, const uint32_t *sec_win,
+                          uint32_t *name_hash, uint32_t *nameval_hash,
+                          uint8_t *kind, uint8_t *static_id, uint32_t *dyn_id,
+                          void *stream);
+
+int qhuff_dyn_lookup_tabs_host(qhuff_ctx *ctx, const uint8_t *in,
+                               const uint32_t *off, uint32_t n,
+                               const uint32_t *sec_hdr, uint32_t m,
+                               const struct qhuff_dyn_tables *tabs,
+                               const uint32_t *sec_tab,
+                               const uint32_t *sec_win, uint32_t *name_hash,
+                               uint32_t *nameval_hash, uint8_t *kind,
+                               uint8_t *static_id, uint32_t *dyn_id);
+
+int qhuff_dyn_lookup_tabs_cpu(const uint8_t *in, const uint32_t *off,
+                              uint32_t n, const uint32_t *sec_hdr, uint32_t m,
+                              const struct qhuff_dyn_tables *tabs,
+                              const uint32_t *sec_tab,
+                              const uint32_t *sec_win, uint32_t *name_hash,
+                              uint32_t *nameval_hash, uint8_t *kind,
+                              uint8_t *static_id, uint32_t *dyn_id);
+
+uint32_t qhuff_dyn_tables_index_slots(uint32_t D);
+
+int qhuff_encode_headers_tabs(qhuff_ctx *ctx, const uint8_t *in,
+                              const uint32_t *off, uint32_t n,
+                              const uint8_t *hflags, const uint32_t *sec_hdr,
+                              uint32_t m, const struct qhuff_dyn_tables *tabs,
+                              const uint32_t *sec_tab,
+                              const uint32_t *sec_win,
+                              const uint32_t *sec_base, uint8_t *out,
+                              uint32_t *sec_out, uint8_t *kind,
+                              uint8_t *static_id, uint32_t *dyn_id,
+                              void *stream);
+
+int qhuff_encode_headers_tabs_host(qhuff_ctx *ctx, const uint8_t *in,
+                                   const uint32_t *off, uint32_t n,
+                                   const uint8_t *hflags,
+                                   const uint32_t *sec_hdr, uint32_t m,
+                                   const struct qhuff_dyn_tables *tabs,
+                                   const uint32_t *sec_tab,
+                                   const uint32_t *sec_win,
+                                   const uint32_t *sec_base, uint8_t *out,
+                                   uint32_t *sec_out, uint8_t *kind,
+                                   uint8_t *static_id, uint32_t *dyn_id);
+
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman
  * payload was precomputed by a QHUFF_ENC_PAYLOAD batch (huff, huff_len =

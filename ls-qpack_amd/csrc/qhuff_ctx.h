@@ -136,6 +136,8 @@ struct qhuff_ctx
     uint32_t dyn_grid[2];                // resident workgroups of its lookup
                                          // kernel ([1]: the encode form's),
                                          // found at the first call
+    uint32_t tabs_grid[2];               // the same of the lookup over a set
+                                         // of tables (qhuff_lookup_tabs.hip)
     char err_msg[256];
 };
 
@@ -183,6 +185,22 @@ namespace qhuff {
 extern thread_local char t_open_err[160];
 int fail(qhuff_ctx *c, hipError_t e, const char *what);
 int mirror_error(qhuff_ctx *c);
+// (qhuff_dyn_lookup_tabs / qhuff_encode_headers_tabs after their checks, with
+// D = ent[T] known to the caller; n and m not 0)
+int tabs_lookup_dev(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                    uint32_t n, const uint32_t *sec_hdr, uint32_t m,
+                    const struct qhuff_dyn_tables *tabs, uint32_t D,
+                    const uint32_t *sec_tab, const uint32_t *sec_win,
+                    uint32_t *name_hash, uint32_t *nameval_hash,
+                    uint8_t *kind, uint8_t *static_id, uint32_t *dyn_id,
+                    hipStream_t st);
+int tabs_encode_dev(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                    uint32_t n, const uint8_t *hflags, const uint32_t *sec_hdr,
+                    uint32_t m, const struct qhuff_dyn_tables *tabs,
+                    uint32_t D, const uint32_t *sec_tab,
+                    const uint32_t *sec_win, const uint32_t *sec_base,
+                    uint8_t *out, uint32_t *sec_out, uint8_t *kind,
+                    uint8_t *static_id, uint32_t *dyn_id, hipStream_t st);
 // qhuff_hostpath.cpp
 void pipe_teardown(qhuff_ctx *c);
 bool host_registered(const void *p, uint64_t bytes);

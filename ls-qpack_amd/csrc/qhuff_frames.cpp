@@ -24,6 +24,7 @@
 #include "qhuff_lookup_dyn_impl.h"
 #include "qhuff_names.h"
 #include "qhuff_scan_impl.h"
+#include "qhuff_tabs_impl.h"
 
 namespace {
 
@@ -576,6 +577,148 @@ qhuff_dyn_lookup_cpu(const uint8_t *in, const uint32_t *off, uint32_t n,
             return QHUFF_EINVAL;
     return dyn_lookup_cpu_run(in, off, n, tab, win_lo, win_hi, name_hash,
                               nameval_hash, kind, static_id, dyn_id);
+}
+
+// ---- ... over a set of tables, a table per section (qhuff_tabs_impl.h) -------
+
+// qhuff_scan_headers_tabs' two passes in plain C++: qhuff_scan_headers_dyn_cpu
+// with each section's window formed from its own table.
+extern "C" int
+qhuff_scan_headers_tabs_cpu(const uint8_t *buf, const uint32_t *sec_off,
+                            uint32_t m, const struct qhuff_dyn_tables *tabs,
+                            const uint32_t *sec_tab, const uint32_t *sec_win,
+                            struct qhuff_hstr *strs, uint32_t max_hdrs,
+                            uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                            uint8_t *static_id, uint8_t *hflags,
+                            uint32_t *dyn_id)
+{
+    namespace qs = qhuff::scan;
+    if (!hdr_off || (m && (!buf || !sec_off || !rc)) || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    for (uint32_t i = 0; i < m; ++i)
+        if (sec_off[i + 1] < sec_off[i])
+            return QHUFF_EINVAL;
+    uint32_t D, longest;
+    if (const int r = qhuff::tabs_check(tabs, sec_tab, sec_win, nullptr, m,
+                                        false, &D, &longest))
+        return r;
+    HostReader r{buf};
+    auto win = [&](uint32_t i) {
+        return qs::dyn_win_tabs(tabs->off, tabs->ent, tabs->first,
+                                tabs->max_entries, tabs->T, D, sec_tab,
+                                sec_win, i);
+    };
+    // the count pass
+    hdr_off[0] = 0;
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        qs::HdrDynCountSink s{0};
+        rc[i] = qs::walk_header_section(r, s, sec_off[i], sec_off[i + 1],
+                                        win(i));
+        hdr_off[i + 1] = hdr_off[i] + s.n;
+    }
+    // the write pass
+    for (uint32_t i = 0; i < m; ++i)
+    {
+        const uint32_t first = hdr_off[i];
+        const uint32_t last = hdr_off[i + 1] < max_hdrs ? hdr_off[i + 1]
+                                                        : max_hdrs;
+        if (hdr_off[i + 1] == first || first >= last)
+            continue;
+        qs::HdrDynWriteSink w{{strs, kind, static_id, hflags, first, last},
+                              dyn_id};
+        (void) qs::walk_header_section(r, w, sec_off[i], sec_off[i + 1],
+                                       win(i));
+    }
+    return hdr_off[m] > max_hdrs ? QHUFF_ERANGE : QHUFF_OK;
+}
+
+extern "C" uint32_t
+qhuff_dyn_tables_index_slots(uint32_t D)
+{
+    return qhuff::dyn_index_slots(D);
+}
+
+// qhuff_dyn_lookup_tabs in plain C++, after the host form's checks: the one
+// pair of indices built entry by entry in ordinal order, each entry's first
+// slot mixed with its table, then the kernel's lookup source section by
+// section, header by header
+extern "C" int
+qhuff_dyn_lookup_tabs_cpu(const uint8_t *in, const uint32_t *off, uint32_t n,
+                          const uint32_t *sec_hdr, uint32_t m,
+                          const struct qhuff_dyn_tables *tabs,
+                          const uint32_t *sec_tab, const uint32_t *sec_win,
+                          uint32_t *name_hash, uint32_t *nameval_hash,
+                          uint8_t *kind, uint8_t *static_id, uint32_t *dyn_id)
+{
+    if (!off || !sec_hdr || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    if (sec_hdr[0] != 0 || sec_hdr[m] != n)
+        return QHUFF_EINVAL;
+    for (uint32_t s = 0; s < m; ++s)
+        if (sec_hdr[s + 1] < sec_hdr[s])
+            return QHUFF_EINVAL;
+    for (uint64_t i = 0; i < 2ull * n; ++i)
+        if (off[i + 1] < off[i])
+            return QHUFF_EINVAL;
+    uint32_t D, longest;
+    if (const int rc = qhuff::tabs_check(tabs, sec_tab, sec_win, nullptr, m,
+                                         true, &D, &longest))
+        return rc;
+    const uint32_t slots = D ? qhuff::dyn_index_slots(D) : 0;
+    uint32_t *idx = slots ? new (std::nothrow) uint32_t[2ull * slots]() : nullptr;
+    if (slots && !idx)
+        return QHUFF_ENOMEM;
+    // all D entries as one table of ordinals
+    qhuff::DynTab<qhuff::HashMem, const uint32_t *> t;
+    t.tb = qhuff::HashMem{tabs->bytes};
+    t.off = tabs->off;
+    t.nv = idx;
+    t.nm = idx + slots;
+    t.mask = slots ? slots - 1 : 0;
+    t.d = D;
+    t.first = 0;
+    t.t0 = D ? tabs->off[0] : 0;
+    t.t1 = D ? tabs->off[2ull * D] : 0;
+    auto claim = [](uint32_t *p, uint32_t v) {
+        if (*p)
+            return false;
+        *p = v;
+        return true;
+    };
+    for (uint32_t k = 0; k < D; ++k)
+        qhuff::dyn_index_insert(
+            t.tb, t.off, k, t.t0, t.t1, idx, idx + slots, t.mask, claim,
+            qhuff::tab_mix(qhuff::tab_of_entry(tabs->ent, tabs->T, D, k)));
+    const qhuff::HashMem r{in};
+    for (uint32_t s = 0; s < m; ++s)
+    {
+        const qhuff::TabSection sec = qhuff::tab_section(
+            tabs->ent, tabs->first, tabs->max_entries, tabs->T, D, sec_tab,
+            sec_win, (const uint32_t *) nullptr, s);
+        for (uint32_t i = sec_hdr[s]; i < sec_hdr[s + 1]; ++i)
+        {
+            const uint32_t a = off[2ull * i], mid = off[2ull * i + 1],
+                           b = off[2ull * i + 2];
+            const uint32_t h1 = qhuff::xxh32(r, a, mid - a, QHUFF_XXH_SEED);
+            const uint32_t h2 = qhuff::xxh32(r, mid, b - mid, h1);
+            const qhuff::DynHit hit = qhuff::tab_hit(
+                qhuff::dyn_lookup(r, a, mid, b, h1, h2, kStaticHost, t,
+                                  sec.glo, sec.ghi, sec.mix), sec.delta);
+            if (name_hash)
+                name_hash[i] = h1;
+            if (nameval_hash)
+                nameval_hash[i] = h2;
+            kind[i] = (uint8_t) hit.kind;
+            static_id[i] = (uint8_t) hit.id;
+            if (dyn_id)
+                dyn_id[i] = hit.dyn;
+        }
+    }
+    delete[] idx;
+    return QHUFF_OK;
 }
 
 extern "C" int

@@ -1574,17 +1574,10 @@ dyn_tab_ok(const struct qhuff_dyn_table *tab)
     return QHUFF_OK;
 }
 
-// The dynamic lookup's scratch for m sections and a table of d entries --
-// [ric: m words | the two indices: qhuff_dyn_index_slots(d) words each, none
-// when d = 0], cleared on st -- and the table's part of the arguments.
-// After hdr_prepare: the scratch is ordered across streams with hdr_ws, by
-// the same event.
+// dyn_ws grown to `words` words and that many cleared on st
 static int
-dyn_prepare(qhuff_ctx *c, const struct qhuff_dyn_table *tab, uint32_t m,
-            hipStream_t st, DynLookupArgs *a)
+dyn_scratch(qhuff_ctx *c, uint64_t words, hipStream_t st)
 {
-    const uint64_t slots = tab->d ? dyn_index_slots(tab->d) : 0;
-    const uint64_t words = (uint64_t) m + 2 * slots;
     if (words > c->dyn_cap)
     {
         if (c->dyn_ws)
@@ -1602,6 +1595,21 @@ dyn_prepare(qhuff_ctx *c, const struct qhuff_dyn_table *tab, uint32_t m,
     }
     if (words)
         HIPCHK(c, hipMemsetAsync(c->dyn_ws, 0, 4 * words, st));
+    return QHUFF_OK;
+}
+
+// The dynamic lookup's scratch for m sections and a table of d entries --
+// [ric: m words | the two indices: qhuff_dyn_index_slots(d) words each, none
+// when d = 0], cleared on st -- and the table's part of the arguments.
+// After hdr_prepare: the scratch is ordered across streams with hdr_ws, by
+// the same event.
+static int
+dyn_prepare(qhuff_ctx *c, const struct qhuff_dyn_table *tab, uint32_t m,
+            hipStream_t st, DynLookupArgs *a)
+{
+    const uint64_t slots = tab->d ? dyn_index_slots(tab->d) : 0;
+    if (const int r = dyn_scratch(c, (uint64_t) m + 2 * slots, st))
+        return r;
     a->tab = tab->d ? tab->bytes : nullptr;
     a->tab_off = tab->d ? tab->off : nullptr;
     a->ric = c->dyn_ws;
@@ -1745,6 +1753,309 @@ qhuff_encode_headers_dyn(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
         return r;
     HIPCHK(c, launch_secout(item_off, sec_hdr, m, n, sec_out, st));
     return QHUFF_OK;
+}
+
+// ---- ... over a set of tables, a table per section ---------------------------
+// (qhuff_hdrscan_tabs.hip, qhuff_lookup_tabs.hip)
+
+// what the device forms can check of a set: a host struct
+static int
+tabs_ok(const struct qhuff_dyn_tables *t, const uint32_t *sec_tab, uint32_t m)
+{
+    if (!t || (t->T && (!t->ent || !t->first || !t->max_entries
+                        || (m && !sec_tab))))
+        return QHUFF_EINVAL;
+    return QHUFF_OK;
+}
+
+// qhuff_scan_headers_dyn's frame over the walker with a table per section.
+// (D is not known here: the kernels read ent[T]; off may be null only when
+// T = 0.)
+extern "C" int
+qhuff_scan_headers_tabs(qhuff_ctx *c, const uint8_t *buf,
+                        const uint32_t *sec_off, uint32_t m,
+                        const struct qhuff_dyn_tables *tabs,
+                        const uint32_t *sec_tab, const uint32_t *sec_win,
+                        struct qhuff_hstr *strs, uint32_t max_hdrs,
+                        uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                        uint8_t *static_id, uint8_t *hflags, uint32_t *dyn_id,
+                        void *stream)
+{
+    if (!c || !hdr_off || (m && (!buf || !sec_off || !rc))
+            || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    if (const int r = tabs_ok(tabs, sec_tab, m))
+        return r;
+    if (tabs->T && !tabs->off)
+        return QHUFF_EINVAL;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (m == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(hdr_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    if (const int r = scan_prepare(c, m, st))
+        return r;
+    HdrScanTabsArgs a;
+    a.h.buf = buf;
+    a.h.sec_off = sec_off;
+    a.h.strs = strs;
+    a.h.hdr_off = hdr_off;
+    a.h.rc = rc;
+    a.h.kind = kind;
+    a.h.static_id = static_id;
+    a.h.hflags = hflags;
+    a.h.cnt = c->scan_ws;
+    a.h.tot = c->scan_ws + c->scan_cap;
+    a.h.m = m;
+    a.h.max_hdrs = max_hdrs;
+    a.off = tabs->off;
+    a.ent = tabs->ent;
+    a.first = tabs->first;
+    a.max_entries = tabs->max_entries;
+    a.sec_tab = tabs->T ? sec_tab : nullptr;
+    a.sec_win = sec_win;
+    a.dyn_id = dyn_id;
+    a.T = tabs->T;
+    ScanArgs top = {};                   // (the top launch reads tot and m)
+    top.tot = a.h.tot;
+    top.m = m;
+    for (unsigned step = 0; step < 3; ++step)
+    {
+        const int r = timed(c, QHUFF_KIND_SCAN, "launch_hdrscan_tabs",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return step == 1 ? launch_scan(top, 1, st, e0, e1)
+                             : launch_hdrscan_tabs(a, step, st, e0, e1);
+        });
+        if (step || !r)
+        {
+            c->scan_stream = st;
+            c->scan_have = true;
+        }
+        if (r)
+            return r;
+    }
+    return QHUFF_OK;
+}
+
+// D = ent[T] of a set in device memory: one 4-byte copy on st, waited for
+static int
+tabs_read_entries(qhuff_ctx *c, const struct qhuff_dyn_tables *t,
+                  hipStream_t st, uint32_t *D)
+{
+    *D = 0;
+    if (!t->T)
+        return QHUFF_OK;
+    HIPCHK(c, hipMemcpyAsync(D, t->ent + t->T, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return QHUFF_OK;
+}
+
+// The tabs lookup's scratch -- dyn_prepare's layout with one pair of indices
+// over all D entries -- and the set's part of the arguments.  After
+// hdr_prepare.
+static int
+tabs_prepare(qhuff_ctx *c, const struct qhuff_dyn_tables *t, uint32_t D,
+             const uint32_t *sec_tab, uint32_t ric_words, hipStream_t st,
+             TabsLookupArgs *a)
+{
+    if (D > kDynMaxD)
+        return QHUFF_ERANGE;
+    if (D && (!t->off || !t->bytes))
+        return QHUFF_EINVAL;
+    const uint64_t slots = D ? dyn_index_slots(D) : 0;
+    if (const int r = dyn_scratch(c, (uint64_t) ric_words + 2 * slots, st))
+        return r;
+    a->tab = D ? t->bytes : nullptr;
+    a->tab_off = D ? t->off : nullptr;
+    a->ent = t->ent;
+    a->first = t->first;
+    a->max_entries = t->max_entries;
+    a->sec_tab = t->T ? sec_tab : nullptr;
+    a->ric = c->dyn_ws;
+    a->nv = slots ? c->dyn_ws + ric_words : nullptr;
+    a->nm = slots ? c->dyn_ws + ric_words + slots : nullptr;
+    a->mask = slots ? (uint32_t) slots - 1 : 0;
+    a->T = t->T;
+    a->D = D;
+    return QHUFF_OK;
+}
+
+// the index build (D != 0) and the lookup, on st
+static int
+tabs_launches(qhuff_ctx *c, const TabsLookupArgs &a, hipStream_t st)
+{
+    if (a.D)
+    {
+        const int r = timed(c, QHUFF_KIND_HASH, "launch_tabs_index",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_tabs_index(a, st, e0, e1);
+        });
+        // (a launch went out: later calls on another stream wait for it)
+        c->hdr_stream = st;
+        c->hdr_have = true;
+        if (r)
+            return r;
+    }
+    const bool enc = a.l.items != nullptr;
+    if (!c->tabs_grid[enc])
+    {
+        // (the workgroups of this kernel that fit at once; any grid is
+        // correct)
+        int occ = 0;
+        HIPCHK(c, lookup_tabs_occupancy(enc, &occ));
+        c->tabs_grid[enc] = (uint32_t) (occ > 0 ? occ : 1) * (uint32_t) c->n_cu;
+    }
+    const int r = timed(c, QHUFF_KIND_HASH, "launch_lookup_tabs",
+                        [&](hipEvent_t e0, hipEvent_t e1) {
+        return launch_lookup_tabs(a, c->tabs_grid[enc], st, e0, e1);
+    });
+    if (!r)
+    {
+        c->hdr_stream = st;
+        c->hdr_have = true;
+    }
+    return r;
+}
+
+// qhuff_dyn_lookup_tabs after its checks, D known (the host form knows it)
+int
+qhuff::tabs_lookup_dev(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                       uint32_t n, const uint32_t *sec_hdr, uint32_t m,
+                       const struct qhuff_dyn_tables *tabs, uint32_t D,
+                       const uint32_t *sec_tab, const uint32_t *sec_win,
+                       uint32_t *name_hash, uint32_t *nameval_hash,
+                       uint8_t *kind, uint8_t *static_id, uint32_t *dyn_id,
+                       hipStream_t st)
+{
+    if (const int r = hdr_prepare(c, 0, st))
+        return r;
+    TabsLookupArgs a = {};
+    a.l = lookup_args(in, off, n, name_hash, nameval_hash, kind, static_id);
+    a.l.sec_hdr = sec_hdr;
+    a.l.m = m;
+    a.sec_win = sec_win;
+    a.dyn_id = dyn_id;
+    if (const int r = tabs_prepare(c, tabs, D, sec_tab, 0, st, &a))
+        return r;
+    return tabs_launches(c, a, st);
+}
+
+extern "C" int
+qhuff_dyn_lookup_tabs(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                      uint32_t n, const uint32_t *sec_hdr, uint32_t m,
+                      const struct qhuff_dyn_tables *tabs,
+                      const uint32_t *sec_tab, const uint32_t *sec_win,
+                      uint32_t *name_hash, uint32_t *nameval_hash,
+                      uint8_t *kind, uint8_t *static_id, uint32_t *dyn_id,
+                      void *stream)
+{
+    if (!c || !off || !sec_hdr || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    if (const int r = tabs_ok(tabs, sec_tab, m))
+        return r;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0)
+        return QHUFF_OK;
+    // (headers without a section: sec_hdr[0] = 0 != n, the caller's breach)
+    if (m == 0)
+        return QHUFF_EINVAL;
+    uint32_t D;
+    if (const int r = tabs_read_entries(c, tabs, st, &D))
+        return r;
+    return tabs_lookup_dev(c, in, off, n, sec_hdr, m, tabs, D, sec_tab,
+                           sec_win, name_hash, nameval_hash, kind, static_id,
+                           dyn_id, st);
+}
+
+// qhuff_encode_headers_tabs after its checks, D known; n and m not 0
+int
+qhuff::tabs_encode_dev(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                       uint32_t n, const uint8_t *hflags,
+                       const uint32_t *sec_hdr, uint32_t m,
+                       const struct qhuff_dyn_tables *tabs, uint32_t D,
+                       const uint32_t *sec_tab, const uint32_t *sec_win,
+                       const uint32_t *sec_base, uint8_t *out,
+                       uint32_t *sec_out, uint8_t *kind, uint8_t *static_id,
+                       uint32_t *dyn_id, hipStream_t st)
+{
+    const uint64_t items = 2ull * n + 2ull * m;
+    if (const int r = hdr_prepare(c, items, st))
+        return r;
+    TabsLookupArgs a = {};
+    a.l = lookup_args(in, off, n, nullptr, nullptr, kind, static_id);
+    a.l.hflags = hflags;
+    a.l.sec_hdr = sec_hdr;
+    a.l.m = m;
+    a.l.items = (struct qhuff_item *) c->hdr_ws;
+    a.l.str_off = (uint32_t *) (c->hdr_ws + 8 * c->hdr_cap);
+    uint32_t *item_off = (uint32_t *) (c->hdr_ws + 8 * c->hdr_cap
+                                       + hdr_up16(4 * (c->hdr_cap + 1)));
+    a.sec_win = sec_win;
+    a.sec_base = sec_base;
+    a.dyn_id = dyn_id;
+    if (const int r = tabs_prepare(c, tabs, D, sec_tab, m, st, &a))
+        return r;
+    int r = tabs_launches(c, a, st);
+    if (r)
+        return r;
+    r = timed(c, QHUFF_KIND_HASH, "launch_tabs_prefix",
+              [&](hipEvent_t e0, hipEvent_t e1) {
+        return launch_tabs_prefix(a, st, e0, e1);
+    });
+    if (r)
+        return r;
+    r = qhuff_encode_wire(c, in, a.l.str_off, a.l.items, (uint32_t) items, out,
+                          item_off, st);
+    if (r)
+        return r;
+    HIPCHK(c, launch_secout(item_off, sec_hdr, m, n, sec_out, st));
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_encode_headers_tabs(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
+                          uint32_t n, const uint8_t *hflags,
+                          const uint32_t *sec_hdr, uint32_t m,
+                          const struct qhuff_dyn_tables *tabs,
+                          const uint32_t *sec_tab, const uint32_t *sec_win,
+                          const uint32_t *sec_base, uint8_t *out,
+                          uint32_t *sec_out, uint8_t *kind, uint8_t *static_id,
+                          uint32_t *dyn_id, void *stream)
+{
+    if (!c || !off || !sec_hdr || !sec_out || (n && !in) || ((n || m) && !out))
+        return QHUFF_EINVAL;
+    if (const int r = tabs_ok(tabs, sec_tab, m))
+        return r;
+    const uint64_t items = 2ull * n + 2ull * m;
+    if (items > 0xffffffffull)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (items == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(sec_out, 0, 4, st));
+        return QHUFF_OK;
+    }
+    // (headers without a section: sec_hdr[0] = 0 != n, the caller's breach)
+    if (m == 0)
+        return QHUFF_EINVAL;
+    if (n == 0)
+    {
+        // (no header, no reference: every section is 00 00)
+        HIPCHK(c, launch_empty_sections(m, out, sec_out, st));
+        return QHUFF_OK;
+    }
+    uint32_t D;
+    if (const int r = tabs_read_entries(c, tabs, st, &D))
+        return r;
+    return tabs_encode_dev(c, in, off, n, hflags, sec_hdr, m, tabs, D, sec_tab,
+                           sec_win, sec_base, out, sec_out, kind, static_id,
+                           dyn_id, st);
 }
 
 // ---- host helpers --------------------------------------------------------------

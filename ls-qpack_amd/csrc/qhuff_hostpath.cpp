@@ -3,6 +3,7 @@
 #include "qhuff_ctx.h"
 #include "qhuff_scan_impl.h"
 #include "qhuff_lookup_dyn_impl.h"
+#include "qhuff_tabs_impl.h"
 
 namespace qhuff {
 // qhuff_frames.cpp: a VALUE literal's static-table name length, or 0
@@ -1883,6 +1884,421 @@ qhuff_encode_headers_dyn_host(qhuff_ctx *c, const uint8_t *in,
                                   D + o_out, (uint32_t *) (D + o_so), D + o_k,
                                   D + o_id, (uint32_t *) (D + o_did),
                                   c->own_stream);
+    if (rc)
+        return rc;
+    if ((rc = stage_down(c, o_so, o_so, o_out, m, out, sec_out)))
+        return rc;
+    if (kind && n)
+        memcpy(kind, c->h_stage + o_k, n);
+    if (static_id && n)
+        memcpy(static_id, c->h_stage + o_id, n);
+    if (dyn_id && n)
+        memcpy(dyn_id, c->h_stage + o_did, 4ull * n);
+    return QHUFF_OK;
+}
+
+// ---- ... over a set of tables, a table per section, host buffers ---------------
+
+// a set's part of a stage: the shared bytes (rebased by -off[0]), the
+// offsets, then the small arrays ent, first and max_entries
+struct TabsUp
+{
+    uint64_t t0, tb;                     // off[0], the bytes held
+    size_t bytes, off, ent, first, me, end;
+    uint32_t D;
+};
+
+static TabsUp
+tabs_up(const struct qhuff_dyn_tables *t, uint32_t D, size_t at)
+{
+    TabsUp u;
+    const uint64_t T = t->T;
+    u.D = D;
+    u.t0 = D ? t->off[0] : 0;
+    u.tb = D ? t->off[2ull * D] - u.t0 : 0;
+    u.bytes = at;
+    u.off = at + up16(u.tb) + 16;
+    u.ent = u.off + up16(D ? 4 * (2ull * D + 1) : 0);
+    u.first = u.ent + up16(T ? 4 * (T + 1) : 0);
+    u.me = u.first + up16(4 * T);
+    u.end = u.me + up16(4 * T);
+    return u;
+}
+
+// the set as the device-pointer calls read it from the stage at D
+static struct qhuff_dyn_tables
+tabs_dev(const struct qhuff_dyn_tables *t, const TabsUp &u, uint8_t *D)
+{
+    struct qhuff_dyn_tables dev = *t;
+    dev.bytes = D + u.bytes - u.t0;
+    dev.off = t->T ? (const uint32_t *) (D + u.off) : nullptr;
+    dev.ent = t->T ? (const uint32_t *) (D + u.ent) : nullptr;
+    dev.first = t->T ? (const uint32_t *) (D + u.first) : nullptr;
+    dev.max_entries = t->T ? (const uint32_t *) (D + u.me) : nullptr;
+    return dev;
+}
+
+#define TABS_STAGE_IN(t, u)                                                  \
+    {(u).tb ? (t)->bytes + (u).t0 : nullptr, (size_t) (u).tb, (u).bytes},    \
+    {(t)->off, (u).D ? (size_t) (4 * (2ull * (u).D + 1)) : 0, (u).off},      \
+    {(t)->ent, (t)->T ? (size_t) (4 * ((t)->T + 1ull)) : 0, (u).ent},        \
+    {(t)->first, (size_t) (4ull * (t)->T), (u).first},                       \
+    {(t)->max_entries, (size_t) (4ull * (t)->T), (u).me}
+
+// dyn_staged with a set of tables: the set, the sections' tables and the
+// windows go up with the wire bytes.  Stage layout: [16 | wire bytes | 16 |
+// sec_off | the set (TabsUp) | sec_tab | sec_win | hdr_off | rc | strs | kind
+// | static_id | hflags | dyn_id], the last five sized for max_hdrs; `extra`
+// more bytes are kept behind them, from o->h.end.
+static int
+tabs_staged(qhuff_ctx *c, const uint8_t *buf, const uint32_t *sec_off,
+            uint32_t m, const struct qhuff_dyn_tables *tabs, uint32_t D_all,
+            const uint32_t *sec_tab, const uint32_t *sec_win,
+            uint32_t max_hdrs, uint32_t *hdr_off, int32_t *rc, uint64_t extra,
+            DynStage *o)
+{
+    const uint64_t a0 = sec_off[0], bytes = (uint64_t) sec_off[m] - a0;
+    const size_t o_so = up16(16 + bytes) + 16;
+    const TabsUp u = tabs_up(tabs, D_all, o_so + up16(4ull * (m + 1)));
+    const bool st = tabs->T != 0;
+    o->tab = u.bytes;
+    const size_t o_st = u.end;
+    const size_t o_sw = o_st + up16(st ? 4ull * m : 0);
+    const size_t o_ho = o_sw + up16(sec_win ? 8ull * m : 0);
+    const size_t o_rc = o_ho + up16(4ull * (m + 1));
+    o->h.strs = o_rc + up16(4ull * m);
+    o->h.kind = o->h.strs + 32ull * max_hdrs;
+    o->h.id = o->h.kind + up16(max_hdrs);
+    o->h.hf = o->h.id + up16(max_hdrs);
+    o->did = o->h.hf + up16(max_hdrs);
+    o->h.end = o->did + up16(4ull * max_hdrs);
+    int r = stage_up(c, o->h.end + extra,
+                     {{buf + a0, bytes, 16}, {sec_off, 4ull * (m + 1), o_so},
+                      TABS_STAGE_IN(tabs, u),
+                      {sec_tab, st ? 4ull * m : 0, o_st},
+                      {sec_win, sec_win ? 8ull * m : 0, o_sw}},
+                     o_ho);
+    if (r)
+        return r;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    const struct qhuff_dyn_tables dev = tabs_dev(tabs, u, D);
+    r = qhuff_scan_headers_tabs(c, D + 16 - a0, (const uint32_t *) (D + o_so),
+                                m, &dev,
+                                st ? (const uint32_t *) (D + o_st) : nullptr,
+                                sec_win ? (const uint32_t *) (D + o_sw)
+                                        : nullptr,
+                                (struct qhuff_hstr *) (D + o->h.strs),
+                                max_hdrs, (uint32_t *) (D + o_ho),
+                                (int32_t *) (D + o_rc), D + o->h.kind,
+                                D + o->h.id, D + o->h.hf,
+                                (uint32_t *) (D + o->did), c->own_stream);
+    if (r)
+        return r;
+    HIPCHK(c, hipMemcpyAsync(H + o_ho, D + o_ho, o->h.strs - o_ho,
+                             hipMemcpyDeviceToHost, c->own_stream));
+    HIPCHK(c, hipStreamSynchronize(c->own_stream));
+    memcpy(hdr_off, H + o_ho, 4ull * (m + 1));
+    memcpy(rc, H + o_rc, 4ull * m);
+    return QHUFF_OK;
+}
+
+extern "C" int
+qhuff_scan_headers_tabs_host(qhuff_ctx *c, const uint8_t *buf,
+                             const uint32_t *sec_off, uint32_t m,
+                             const struct qhuff_dyn_tables *tabs,
+                             const uint32_t *sec_tab, const uint32_t *sec_win,
+                             struct qhuff_hstr *strs, uint32_t max_hdrs,
+                             uint32_t *hdr_off, int32_t *rc, uint8_t *kind,
+                             uint8_t *static_id, uint8_t *hflags,
+                             uint32_t *dyn_id)
+{
+    if (!hdr_args_ok(c, buf, sec_off, m, hdr_off, rc) || (max_hdrs && !strs))
+        return QHUFF_EINVAL;
+    uint32_t D_all, longest;
+    if (const int r = tabs_check(tabs, sec_tab, sec_win, nullptr, m, false,
+                                 &D_all, &longest))
+        return r;
+    if (m == 0)
+    {
+        hdr_off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    DynStage o;
+    int r = tabs_staged(c, buf, sec_off, m, tabs, D_all, sec_tab, sec_win,
+                        max_hdrs, hdr_off, rc, 0, &o);
+    if (r)
+        return r;
+    const uint32_t n = hdr_off[m] < max_hdrs ? hdr_off[m] : max_hdrs;
+    if (n)
+    {
+        uint8_t *H = c->h_stage, *D = c->d_stage;
+        HIPCHK(c, hipMemcpyAsync(H + o.h.strs, D + o.h.strs, 32ull * n,
+                                 hipMemcpyDeviceToHost, c->own_stream));
+        HIPCHK(c, hipMemcpyAsync(H + o.h.kind, D + o.h.kind,
+                                 o.did + 4ull * n - o.h.kind,
+                                 hipMemcpyDeviceToHost, c->own_stream));
+        HIPCHK(c, hipStreamSynchronize(c->own_stream));
+        memcpy(strs, H + o.h.strs, 32ull * n);
+        hdr_bytes_out(c, o.h, n, kind, static_id, hflags);
+        if (dyn_id)
+            memcpy(dyn_id, H + o.did, 4ull * n);
+    }
+    return hdr_off[m] > max_hdrs ? QHUFF_ERANGE : QHUFF_OK;
+}
+
+// The whole path, as qhuff_decode_headers_dyn_host: tabs_staged, then
+// qhuff_decode_headers_dyn unchanged on the descriptors and on the shared
+// bytes where they lie.
+extern "C" int
+qhuff_decode_headers_tabs_host(qhuff_ctx *c, const uint8_t *buf,
+                               const uint32_t *sec_off, uint32_t m,
+                               const struct qhuff_dyn_tables *tabs,
+                               const uint32_t *sec_tab,
+                               const uint32_t *sec_win, uint32_t max_len,
+                               uint32_t max_hdrs, uint32_t *hdr_off,
+                               int32_t *rc, uint8_t *kind, uint8_t *static_id,
+                               uint8_t *hflags, uint32_t *dyn_id, uint8_t *out,
+                               uint32_t *off, uint8_t *status,
+                               uint32_t *name_hash, uint32_t *nameval_hash)
+{
+    if (!off || !hdr_args_ok(c, buf, sec_off, m, hdr_off, rc)
+            || (max_hdrs && (!out || !status)))
+        return QHUFF_EINVAL;
+    if (max_hdrs > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    uint32_t D_all, longest;
+    if (const int r = tabs_check(tabs, sec_tab, sec_win, nullptr, m, false,
+                                 &D_all, &longest))
+        return r;
+    if (m == 0)
+    {
+        hdr_off[0] = 0;
+        off[0] = 0;
+        return QHUFF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t bytes = (uint64_t) sec_off[m] - sec_off[0];
+    const uint64_t bound = qhuff_decode_headers_dyn_bound(bytes, max_hdrs,
+                                                          longest);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    const uint64_t mh = max_hdrs;
+    DynStage o;
+    int r = tabs_staged(c, buf, sec_off, m, tabs, D_all, sec_tab, sec_win,
+                        max_hdrs, hdr_off, rc,
+                        up16(4 * (2 * mh + 1)) + up16(2 * mh)
+                            + 2 * up16(4 * mh) + up16(bound),
+                        &o);
+    if (r)
+        return r;
+    const uint32_t n = hdr_off[m];
+    if (n > max_hdrs)
+        return QHUFF_ERANGE;
+    const size_t o_off = o.h.end;
+    const size_t o_st = o_off + up16(4 * (2ull * n + 1));
+    const size_t o_h1 = o_st + up16(2ull * n);
+    const size_t o_h2 = o_h1 + up16(4ull * n);
+    const size_t o_out = o_h2 + up16(4ull * n);
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    const uint32_t t0 = D_all ? tabs->off[0] : 0;
+    const uint32_t t1 = D_all ? tabs->off[2ull * D_all] : 0;
+    // (dyn_bytes rebased as the scan's: instr is an offset from tabs->bytes)
+    r = qhuff_decode_headers_dyn(c, D + 16 - sec_off[0],
+                                 (const struct qhuff_hstr *) (D + o.h.strs), n,
+                                 max_len, t1 ? D + o.tab - t0 : nullptr, t1,
+                                 D + o_out, (uint32_t *) (D + o_off),
+                                 D + o_st, c->own_stream);
+    if (r)
+        return r;
+    if (n && (name_hash || nameval_hash))
+    {
+        r = qhuff_xxh32_headers(c, D + o_out, (const uint32_t *) (D + o_off),
+                                n, QHUFF_XXH_SEED, (uint32_t *) (D + o_h1),
+                                (uint32_t *) (D + o_h2), c->own_stream);
+        if (r)
+            return r;
+    }
+    if ((r = stage_down(c, o.h.kind, o_off, o_out, 2 * n, out, off)))
+        return r;
+    if (n)
+    {
+        hdr_bytes_out(c, o.h, n, kind, static_id, hflags);
+        if (dyn_id)
+            memcpy(dyn_id, H + o.did, 4ull * n);
+        memcpy(status, H + o_st, 2ull * n);
+        if (name_hash)
+            memcpy(name_hash, H + o_h1, 4ull * n);
+        if (nameval_hash)
+            memcpy(nameval_hash, H + o_h2, 4ull * n);
+    }
+    return QHUFF_OK;
+}
+
+// the checks the section-wise host forms make of sec_hdr
+static int
+sections_ok(const uint32_t *sec_hdr, uint32_t m, uint32_t n)
+{
+    if (sec_hdr[0] != 0 || sec_hdr[m] != n)
+        return QHUFF_EINVAL;
+    for (uint32_t s = 0; s < m; ++s)
+        if (sec_hdr[s + 1] < sec_hdr[s])
+            return QHUFF_EINVAL;
+    return QHUFF_OK;
+}
+
+// Stage layout: [name/value bytes | offsets (2n + 1) | sec_hdr | the set |
+// sec_tab | sec_win | name_hash | nameval_hash | dyn_id | kind | static_id].
+extern "C" int
+qhuff_dyn_lookup_tabs_host(qhuff_ctx *c, const uint8_t *in,
+                           const uint32_t *off, uint32_t n,
+                           const uint32_t *sec_hdr, uint32_t m,
+                           const struct qhuff_dyn_tables *tabs,
+                           const uint32_t *sec_tab, const uint32_t *sec_win,
+                           uint32_t *name_hash, uint32_t *nameval_hash,
+                           uint8_t *kind, uint8_t *static_id, uint32_t *dyn_id)
+{
+    if (!c || !off || !sec_hdr || (n && (!in || !kind || !static_id)))
+        return QHUFF_EINVAL;
+    if (n > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    if (const int rc = sections_ok(sec_hdr, m, n))
+        return rc;
+    if (const int rc = headers_ok(off, n))
+        return rc;
+    uint32_t D_all, longest;
+    if (const int rc = tabs_check(tabs, sec_tab, sec_win, nullptr, m, true,
+                                  &D_all, &longest))
+        return rc;
+    if (n == 0)
+        return QHUFF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool stb = tabs->T != 0;
+    const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
+    const size_t o_off = up16(bytes) + 16;
+    const size_t o_sh = o_off + up16(4ull * (2ull * n + 1));
+    const TabsUp u = tabs_up(tabs, D_all, o_sh + up16(4ull * (m + 1ull)));
+    const size_t o_st = u.end;
+    const size_t o_sw = o_st + up16(stb ? 4ull * m : 0);
+    const size_t o_h1 = o_sw + up16(sec_win ? 8ull * m : 0);
+    const size_t o_h2 = o_h1 + up16(4ull * n), o_did = o_h2 + up16(4ull * n);
+    const size_t o_k = o_did + up16(4ull * n);
+    const size_t o_id = o_k + up16(n), total = o_id + up16(n);
+    int rc = stage_up(c, total,
+                      {{bytes ? in + a0 : nullptr, bytes, 0},
+                       {off, 4ull * (2ull * n + 1), o_off},
+                       {sec_hdr, 4ull * (m + 1ull), o_sh},
+                       TABS_STAGE_IN(tabs, u),
+                       {sec_tab, stb ? 4ull * m : 0, o_st},
+                       {sec_win, sec_win ? 8ull * m : 0, o_sw}},
+                      o_h1);
+    if (rc)
+        return rc;
+    uint8_t *H = c->h_stage, *D = c->d_stage;
+    hipStream_t st = c->own_stream;
+    const struct qhuff_dyn_tables dev = tabs_dev(tabs, u, D);
+    rc = tabs_lookup_dev(c, D - a0, (const uint32_t *) (D + o_off), n,
+                         (const uint32_t *) (D + o_sh), m, &dev, D_all,
+                         stb ? (const uint32_t *) (D + o_st) : nullptr,
+                         sec_win ? (const uint32_t *) (D + o_sw) : nullptr,
+                         (uint32_t *) (D + o_h1), (uint32_t *) (D + o_h2),
+                         D + o_k, D + o_id, (uint32_t *) (D + o_did), st);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(H + o_h1, D + o_h1, total - o_h1,
+                             hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (name_hash)
+        memcpy(name_hash, H + o_h1, 4ull * n);
+    if (nameval_hash)
+        memcpy(nameval_hash, H + o_h2, 4ull * n);
+    if (dyn_id)
+        memcpy(dyn_id, H + o_did, 4ull * n);
+    memcpy(kind, H + o_k, n);
+    memcpy(static_id, H + o_id, n);
+    return QHUFF_OK;
+}
+
+// Header lists to field sections against a set of tables
+// (qhuff_encode_headers_tabs), as qhuff_encode_headers_dyn_host.  Stage
+// layout: [bytes | off | hflags | sec_hdr | the set | sec_tab | sec_win |
+// sec_base | sec_out | dyn_id | kind | static_id | out].
+extern "C" int
+qhuff_encode_headers_tabs_host(qhuff_ctx *c, const uint8_t *in,
+                               const uint32_t *off, uint32_t n,
+                               const uint8_t *hflags, const uint32_t *sec_hdr,
+                               uint32_t m, const struct qhuff_dyn_tables *tabs,
+                               const uint32_t *sec_tab,
+                               const uint32_t *sec_win,
+                               const uint32_t *sec_base, uint8_t *out,
+                               uint32_t *sec_out, uint8_t *kind,
+                               uint8_t *static_id, uint32_t *dyn_id)
+{
+    if (!c || !off || !sec_hdr || !sec_out || (n && !in) || ((n || m) && !out))
+        return QHUFF_EINVAL;
+    if (2ull * n + 2ull * m > 0xffffffffull)
+        return QHUFF_ERANGE;
+    if (const int rc = sections_ok(sec_hdr, m, n))
+        return rc;
+    if (const int rc = headers_ok(off, n))
+        return rc;
+    uint32_t D_all, longest;
+    if (const int rc = tabs_check(tabs, sec_tab, sec_win, sec_base, m, true,
+                                  &D_all, &longest))
+        return rc;
+    if (m == 0)
+    {
+        sec_out[0] = 0;
+        return QHUFF_OK;
+    }
+    const uint64_t a0 = off[0], bytes = (uint64_t) off[2ull * n] - a0;
+    const uint64_t bound = qhuff_encode_headers_bound(bytes, n, m);
+    if (bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool stb = tabs->T != 0;
+    const size_t o_off = up16(bytes) + 16;
+    const size_t o_fl = o_off + up16(4ull * (2ull * n + 1));
+    const size_t o_sh = o_fl + up16(n);
+    const TabsUp u = tabs_up(tabs, D_all, o_sh + up16(4ull * (m + 1ull)));
+    const size_t o_st = u.end;
+    const size_t o_sw = o_st + up16(stb ? 4ull * m : 0);
+    const size_t o_sb = o_sw + up16(sec_win ? 8ull * m : 0);
+    const size_t o_so = o_sb + up16(sec_base ? 4ull * m : 0);
+    const size_t o_did = o_so + up16(4ull * (m + 1ull));
+    const size_t o_k = o_did + up16(4ull * n);
+    const size_t o_id = o_k + up16(n), o_out = o_id + up16(n);
+    int rc = stage_up(c, o_out + up16(bound),
+                      {{bytes ? in + a0 : nullptr, bytes, 0},
+                       {off, 4ull * (2ull * n + 1), o_off},
+                       {hflags, hflags ? (size_t) n : 0, o_fl},
+                       {sec_hdr, 4ull * (m + 1ull), o_sh},
+                       TABS_STAGE_IN(tabs, u),
+                       {sec_tab, stb ? 4ull * m : 0, o_st},
+                       {sec_win, sec_win ? 8ull * m : 0, o_sw},
+                       {sec_base, sec_base ? 4ull * m : 0, o_sb}}, o_so);
+    if (rc)
+        return rc;
+    uint8_t *D = c->d_stage;
+    hipStream_t st = c->own_stream;
+    const struct qhuff_dyn_tables dev = tabs_dev(tabs, u, D);
+    if (n == 0)
+        rc = qhuff_encode_headers_tabs(
+            c, D - a0, (const uint32_t *) (D + o_off), n, nullptr,
+            (const uint32_t *) (D + o_sh), m, &dev,
+            stb ? (const uint32_t *) (D + o_st) : nullptr, nullptr, nullptr,
+            D + o_out, (uint32_t *) (D + o_so), D + o_k, D + o_id,
+            (uint32_t *) (D + o_did), st);
+    else
+        rc = tabs_encode_dev(c, D - a0, (const uint32_t *) (D + o_off), n,
+                             hflags ? D + o_fl : nullptr,
+                             (const uint32_t *) (D + o_sh), m, &dev, D_all,
+                             stb ? (const uint32_t *) (D + o_st) : nullptr,
+                             sec_win ? (const uint32_t *) (D + o_sw) : nullptr,
+                             sec_base ? (const uint32_t *) (D + o_sb)
+                                      : nullptr,
+                             D + o_out, (uint32_t *) (D + o_so), D + o_k,
+                             D + o_id, (uint32_t *) (D + o_did), st);
     if (rc)
         return rc;
     if ((rc = stage_down(c, o_so, o_so, o_out, m, out, sec_out)))

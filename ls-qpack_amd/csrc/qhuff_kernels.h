@@ -178,6 +178,45 @@ struct DynLookupArgs
     uint32_t win_lo, win_hi;
 };
 
+// the header scan over a set of tables, a table per section
+// (qhuff_hdrscan_tabs.hip; struct qhuff_dyn_tables): the shared offsets, the
+// tables' bounds and each section's table and window.  The kernels read D =
+// ent[T] themselves.  T = 0: every pointer of the set may be null.
+struct HdrScanTabsArgs
+{
+    HdrScanArgs h;
+    const uint32_t *off;         // 2D + 1, or null when D = 0
+    const uint32_t *ent;         // T + 1
+    const uint32_t *first;       // T
+    const uint32_t *max_entries; // T
+    const uint32_t *sec_tab;     // m
+    const uint32_t *sec_win;     // 2m, or null
+    uint32_t *dyn_id;            // max_hdrs, or null
+    uint32_t T;
+};
+
+// headers looked up in the static table and in their section's table of a
+// set (qhuff_lookup_tabs.hip): DynLookupArgs with one pair of indices over
+// all D entries (slots hold global ordinals + 1) and a table per section.
+// Both forms go by sections (l.sec_hdr, l.m); lookup form: l.items = null,
+// no sec_base, no ric.
+struct TabsLookupArgs
+{
+    LookupArgs l;
+    const uint8_t *tab;          // the shared bytes, or null when D = 0
+    const uint32_t *tab_off;     // 2D + 1, or null when D = 0
+    const uint32_t *ent;         // T + 1
+    const uint32_t *first;       // T
+    const uint32_t *max_entries; // T
+    uint32_t *nv, *nm;           // by name+value hash, by name hash
+    const uint32_t *sec_tab;     // m (null when T = 0)
+    const uint32_t *sec_win;     // 2m, or null
+    const uint32_t *sec_base;    // m, or null
+    uint32_t *dyn_id;            // n, or null
+    uint32_t *ric;               // m: 1 + the largest index a section named
+    uint32_t T, D, mask;
+};
+
 // ---- low-latency service (qhuff_service.hip, qhuff_svc_host.cpp) ----------
 //
 // One request slot per service wave, in pinned host memory mapped into the
@@ -347,6 +386,22 @@ hipError_t launch_dyn_prefix(const DynLookupArgs &a, hipStream_t st,
                              hipEvent_t ev1 = nullptr);
 // (enc: of the encode form's kernel, else of the lookup form's)
 hipError_t lookup_dyn_occupancy(bool enc, int *blocks_per_cu);
+// the same launches over a set of tables (qhuff_hdrscan_tabs.hip,
+// qhuff_lookup_tabs.hip): the index build (a.D != 0), the lookup (a.l.n != 0,
+// a.l.m != 0), the prefix items (encode form)
+hipError_t launch_hdrscan_tabs(const HdrScanTabsArgs &a, unsigned step,
+                               hipStream_t st, hipEvent_t ev0 = nullptr,
+                               hipEvent_t ev1 = nullptr);
+hipError_t launch_tabs_index(const TabsLookupArgs &a, hipStream_t st,
+                             hipEvent_t ev0 = nullptr,
+                             hipEvent_t ev1 = nullptr);
+hipError_t launch_lookup_tabs(const TabsLookupArgs &a, uint32_t max_grid,
+                              hipStream_t st, hipEvent_t ev0 = nullptr,
+                              hipEvent_t ev1 = nullptr);
+hipError_t launch_tabs_prefix(const TabsLookupArgs &a, hipStream_t st,
+                              hipEvent_t ev0 = nullptr,
+                              hipEvent_t ev1 = nullptr);
+hipError_t lookup_tabs_occupancy(bool enc, int *blocks_per_cu);
 // m sections of no headers: out = m x "00 00", sec_out[s] = 2s, s in [0, m]
 hipError_t launch_empty_sections(uint32_t m, uint8_t *out, uint32_t *sec_out,
                                  hipStream_t st);

@@ -77,21 +77,23 @@ dyn_entry(P off, uint32_t k, uint32_t t0, uint32_t t1)
 }
 
 // Entry k into both indices.  cas(p, v): *p == 0 ? (*p = v, true) : false,
-// atomically where lanes run this side by side.
+// atomically where lanes run this side by side.  x is XOR-ed into both
+// hashes for the first slot (0; over a set of tables: the mix of the entry's
+// table, qhuff_tabs_impl.h).
 template <class TB, class P, class W, class CAS>
 QH_HDI void
 dyn_index_insert(const TB &tb, P off, uint32_t k, uint32_t t0, uint32_t t1,
-                 W nv, W nm, uint32_t mask, const CAS &cas)
+                 W nv, W nm, uint32_t mask, const CAS &cas, uint32_t x = 0)
 {
     const DynEntry e = dyn_entry(off, k, t0, t1);
     const uint32_t h1 = xxh32(tb, e.a, e.m - e.a, QHUFF_XXH_SEED);
     const uint32_t h2 = xxh32(tb, e.m, e.b - e.m, h1);
     // (at most mask + 1 steps: it ends whatever the slots hold)
-    uint32_t i = h2 & mask;
+    uint32_t i = (h2 ^ x) & mask;
     for (uint32_t steps = 0; steps <= mask; ++steps, i = (i + 1) & mask)
         if (cas(nv + i, k + 1))
             break;
-    i = h1 & mask;
+    i = (h1 ^ x) & mask;
     for (uint32_t steps = 0; steps <= mask; ++steps, i = (i + 1) & mask)
         if (cas(nm + i, k + 1))
             break;
@@ -159,23 +161,24 @@ dyn_probe(const R &r, uint32_t a, uint32_t nl, uint32_t vl, uint32_t h,
 // The header with name r[a, m) and value r[m, b), hashed to h1 and h2,
 // against the static table and the entries in [lo, hi), in the reference's
 // order: static full, dynamic full, static name, dynamic name, literal.
+// x: what the index build XOR-ed into its entries' first slots.
 template <class R, class TB, class P>
 QH_HDI DynHit
 dyn_lookup(const R &r, uint32_t a, uint32_t m, uint32_t b, uint32_t h1,
            uint32_t h2, const StaticTable &st, const DynTab<TB, P> &t,
-           uint32_t lo, uint32_t hi)
+           uint32_t lo, uint32_t hi, uint32_t x = 0)
 {
     const StaticHit s = static_lookup(r, a, m, b, h1, h2, st);
     if (s.kind == QHUFF_LINE_INDEXED || hi <= lo)
         return DynHit{s.kind, s.id, QHUFF_DYN_NONE};
     const uint32_t nl = m - a, vl = b - m;
     uint32_t best = 0;
-    if (dyn_probe<true>(r, a, nl, vl, h2, t, lo, hi, &best))
+    if (dyn_probe<true>(r, a, nl, vl, h2 ^ x, t, lo, hi, &best))
         return DynHit{QHUFF_LINE_INDEXED | QHUFF_LINE_DYN, QHUFF_STATIC_NONE,
                       best};
     if (s.kind == QHUFF_LINE_NAMEREF)
         return DynHit{s.kind, s.id, QHUFF_DYN_NONE};
-    if (dyn_probe<false>(r, a, nl, vl, h1, t, lo, hi, &best))
+    if (dyn_probe<false>(r, a, nl, vl, h1 ^ x, t, lo, hi, &best))
         return DynHit{QHUFF_LINE_NAMEREF | QHUFF_LINE_DYN, QHUFF_STATIC_NONE,
                       best};
     return DynHit{QHUFF_LINE_LITERAL, QHUFF_STATIC_NONE, QHUFF_DYN_NONE};

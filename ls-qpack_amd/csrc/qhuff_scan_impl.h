@@ -398,6 +398,47 @@ struct DynWin
     }
 };
 
+// ---- a set of tables and a table per section (struct qhuff_dyn_tables) ------
+//
+// Table c of a set as one table: its entries are the ordinals [e0, e0 + d)
+// of the shared arrays.
+struct TabView
+{
+    uint32_t c, e0, d, first, max_entries;
+};
+
+// The table of section s.  P: a pointer to const uint32_t (plain, or in the
+// global address space).  Whatever the arrays hold: sec_tab[s] is clamped to
+// T - 1 and ent values to D, a decreasing pair is an empty table, so e0 + d
+// <= D.  T = 0 (or no sec_tab): a table with d = 0 and max_entries = 0.
+template <class P>
+QH_HD inline TabView
+tab_view(P ent, P first, P max_entries, uint32_t T, uint32_t D, P sec_tab,
+         uint64_t s)
+{
+    if (!T || !sec_tab)
+        return TabView{0, 0, 0, 0, 0};
+    uint32_t c = sec_tab[s];
+    c = c < T ? c : T - 1;
+    uint32_t e0 = ent[c], e1 = ent[c + 1];
+    e0 = e0 < D ? e0 : D;
+    e1 = e1 < D ? e1 : D;
+    return TabView{c, e0, e1 > e0 ? e1 - e0 : 0u, first[c], max_entries[c]};
+}
+
+// DynWin::of for section s of a batch over a set of tables: one load of
+// sec_tab[s], then the table's four words; the offsets based at the table's
+// first entry, the window clamped into the table
+QH_HD inline DynWin
+dyn_win_tabs(const uint32_t *off, const uint32_t *ent, const uint32_t *first,
+             const uint32_t *max_entries, uint32_t T, uint32_t D,
+             const uint32_t *sec_tab, const uint32_t *sec_win, uint64_t s)
+{
+    const TabView v = tab_view(ent, first, max_entries, T, D, sec_tab, s);
+    return DynWin::of(off + 2ull * v.e0, v.d, v.first, v.max_entries, sec_win,
+                      s);
+}
+
 // the host forms' check of a table and of m windows: QHUFF_OK, QHUFF_EINVAL
 // (a null pointer with d != 0, decreasing offsets, a window outside the
 // rule) or QHUFF_ERANGE (first + d passes 2^32 - 1); *longest = the longest

@@ -64,6 +64,11 @@ EXPORTS = (
     "qhuff_dyn_lookup", "qhuff_dyn_lookup_host", "qhuff_dyn_lookup_cpu",
     "qhuff_dyn_index_slots", "qhuff_encode_headers_dyn_bound",
     "qhuff_encode_headers_dyn", "qhuff_encode_headers_dyn_host",
+    "qhuff_scan_headers_tabs", "qhuff_scan_headers_tabs_host",
+    "qhuff_scan_headers_tabs_cpu", "qhuff_decode_headers_tabs_host",
+    "qhuff_dyn_lookup_tabs", "qhuff_dyn_lookup_tabs_host",
+    "qhuff_dyn_lookup_tabs_cpu", "qhuff_dyn_tables_index_slots",
+    "qhuff_encode_headers_tabs", "qhuff_encode_headers_tabs_host",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -432,6 +437,39 @@ def lib():
                                                     vp, vp, C.c_uint32, dtp,
                                                     vp, vp, vp, vp, vp, vp,
                                                     vp]
+        # (the _dyn calls' lists with `tabs, sec_tab` where `tab` stands)
+        tsp = C.POINTER(DynTables)
+        u32 = C.c_uint32
+        L.qhuff_scan_headers_tabs.restype = C.c_int
+        L.qhuff_scan_headers_tabs.argtypes = [vp, vp, vp, u32, tsp, vp, vp,
+                                              vp, u32] + [vp] * 7
+        L.qhuff_scan_headers_tabs_host.restype = C.c_int
+        L.qhuff_scan_headers_tabs_host.argtypes = [vp, vp, u32p, u32, tsp, vp,
+                                                   vp, vp, u32] + [vp] * 6
+        L.qhuff_scan_headers_tabs_cpu.restype = C.c_int
+        L.qhuff_scan_headers_tabs_cpu.argtypes = [vp, u32p, u32, tsp, vp, vp,
+                                                  vp, u32] + [vp] * 6
+        L.qhuff_decode_headers_tabs_host.restype = C.c_int
+        L.qhuff_decode_headers_tabs_host.argtypes = [vp, vp, u32p, u32, tsp,
+                                                     vp, vp, u32, u32] \
+            + [vp] * 11
+        L.qhuff_dyn_lookup_tabs.restype = C.c_int
+        L.qhuff_dyn_lookup_tabs.argtypes = [vp, vp, vp, u32, vp, u32, tsp] \
+            + [vp] * 8
+        L.qhuff_dyn_lookup_tabs_host.restype = C.c_int
+        L.qhuff_dyn_lookup_tabs_host.argtypes = [vp, vp, vp, u32, vp, u32,
+                                                 tsp] + [vp] * 7
+        L.qhuff_dyn_lookup_tabs_cpu.restype = C.c_int
+        L.qhuff_dyn_lookup_tabs_cpu.argtypes = [vp, vp, u32, vp, u32, tsp] \
+            + [vp] * 7
+        L.qhuff_dyn_tables_index_slots.restype = C.c_uint32
+        L.qhuff_dyn_tables_index_slots.argtypes = [u32]
+        L.qhuff_encode_headers_tabs.restype = C.c_int
+        L.qhuff_encode_headers_tabs.argtypes = [vp, vp, vp, u32, vp, vp, u32,
+                                                tsp] + [vp] * 9
+        L.qhuff_encode_headers_tabs_host.restype = C.c_int
+        L.qhuff_encode_headers_tabs_host.argtypes = [vp, vp, vp, u32, vp, vp,
+                                                     u32, tsp] + [vp] * 8
         L.qhuff_decode_headers_host.restype = C.c_int
         L.qhuff_decode_headers_host.argtypes = [vp, vp, u32p, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, u32p,
@@ -671,6 +709,110 @@ def scan_headers_dyn_cpu(buf, sec_off, table, sec_win=None, max_hdrs=None):
     n = min(int(hdr_off[-1]), max_hdrs)
     return (ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n], hf[:n],
             did[:n])
+
+
+class DynTables(C.Structure):
+    """struct qhuff_dyn_tables"""
+    _fields_ = [("bytes", C.c_void_p), ("off", C.c_void_p),
+                ("ent", C.c_void_p), ("first", C.c_void_p),
+                ("max_entries", C.c_void_p), ("T", C.c_uint32)]
+
+
+def dyn_tables_host(data=None, off=None, ent=None, first=None,
+                    max_entries=None):
+    """A set of T dynamic tables as host arrays -> (DynTables, the arrays it
+    points to): data / off the packed entries of all tables (off uint32 [2D +
+    1]), ent uint32 [T + 1] the tables' bounds in entry ordinals, first and
+    max_entries uint32 [T].  ent None: T = 0, every pointer null.  The arrays
+    are passed as they are (the checks are the library's)."""
+    import numpy as np
+    if ent is None:
+        return DynTables(None, None, None, None, None, 0), ()
+    u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)  # noqa: E731
+    ent, first, max_entries = u32(ent), u32(first), u32(max_entries)
+    off = np.zeros(1, np.uint32) if off is None else u32(off)
+    data = np.ascontiguousarray(data if data is not None else [],
+                                dtype=np.uint8)
+    if not len(data):
+        data = np.zeros(1, dtype=np.uint8)
+    t = DynTables(_np_ptr(data), _np_ptr(off), _np_ptr(ent), _np_ptr(first),
+                  _np_ptr(max_entries), len(first))
+    return t, (data, off, ent, first, max_entries)
+
+
+def _tabs_longest(tables):
+    """the longest name + value of a set's entries"""
+    off = tables[1] if len(tables) > 1 else None
+    if off is None or len(off) < 3:
+        return 0
+    import numpy as np
+    off = np.asarray(off, dtype=np.int64)
+    return max(int((off[2::2] - off[:-2:2]).max()), 0)
+
+
+def _opt_u32(a):
+    import numpy as np
+    return None if a is None else \
+        np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+
+
+def _opt_ptr(a):
+    return _np_ptr(a) if a is not None and len(a) else None
+
+
+def dyn_tables_index_slots(D):
+    """qhuff_dyn_tables_index_slots: the slots of each of the two indices a
+    lookup over a set of tables builds over its D entries."""
+    return int(lib().qhuff_dyn_tables_index_slots(D))
+
+
+def scan_headers_tabs_cpu(buf, sec_off, tables, sec_tab, sec_win=None,
+                          max_hdrs=None):
+    """qhuff_scan_headers_tabs_cpu: scan_headers_dyn_cpu with a table per
+    section.  tables: (data, off, ent, first, max_entries) as dyn_tables_host
+    takes them (() or None: T = 0); sec_tab uint32 [m] -> as
+    scan_headers_dyn_cpu."""
+    import numpy as np
+    if max_hdrs is None:
+        max_hdrs = int(scan_headers_tabs_cpu(buf, sec_off, tables, sec_tab,
+                                             sec_win, 0)[2][-1])
+    buf, sec_off, m, strs, hdr_off, rc, kind, sid, hf = \
+        _headers_host_args(buf, sec_off, max_hdrs)
+    did = np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+    t, keep = dyn_tables_host(*(tables or ()))
+    tab, win = _opt_u32(sec_tab), _sec_win_host(sec_win)
+    ret = lib().qhuff_scan_headers_tabs_cpu(
+        _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off), m, C.byref(t),
+        _opt_ptr(tab), _np_ptr(win) if win is not None else None,
+        _np_ptr(strs), max_hdrs, _np_ptr(hdr_off), _np_ptr(rc), _np_ptr(kind),
+        _np_ptr(sid), _np_ptr(hf), _np_ptr(did))
+    del keep
+    n = min(int(hdr_off[-1]), max_hdrs)
+    return (ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n], hf[:n],
+            did[:n])
+
+
+def dyn_lookup_tabs_cpu(data, off, sec_hdr, tables, sec_tab, sec_win=None):
+    """qhuff_dyn_lookup_tabs_cpu: the lookup kernel's source run on the host,
+    header j of section s (sec_hdr uint32 [m + 1]) in table sec_tab[s] within
+    sec_win[2s .. 2s + 1] (None: the whole of that table) -> (ret, name_hash,
+    nameval_hash uint32 [n], kind, static_id uint8 [n], dyn_id uint32 [n])."""
+    import numpy as np
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint32)
+    sec_hdr = np.ascontiguousarray(sec_hdr, dtype=np.uint32)
+    n, m = (len(off) - 1) // 2, len(sec_hdr) - 1
+    h1, h2, did = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+    kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+    t, keep = dyn_tables_host(*(tables or ()))
+    tab, win = _opt_u32(sec_tab), _sec_win_host(sec_win)
+    ret = lib().qhuff_dyn_lookup_tabs_cpu(
+        _np_ptr(data) if len(data) else _np_ptr(np.zeros(1, np.uint8)),
+        _np_ptr(off), n, _np_ptr(sec_hdr), m, C.byref(t), _opt_ptr(tab),
+        _opt_ptr(win), _np_ptr(h1), _np_ptr(h2), _np_ptr(kind), _np_ptr(sid),
+        _np_ptr(did))
+    del keep
+    return ret, h1[:n], h2[:n], kind[:n], sid[:n], did[:n]
 
 
 def hstrs_array(strs):
@@ -1664,6 +1806,230 @@ class Codec:
         res = (ret, hdr_off, rc[:m], kind[:n], sid[:n], hf[:n], did[:n],
                out[:off[2 * n]], off[:2 * n + 1], status[:2 * n])
         return res + ((h1[:n], h2[:n]) if hashes else ())
+
+    # ... over a set of tables, a table per section ---------------------------
+    @staticmethod
+    def dyn_tables_dev(tab_data, tab_off, ent, first, max_entries):
+        """struct qhuff_dyn_tables of device tensors: tab_data uint8, tab_off
+        int32 [2D + 1], ent int32 [T + 1], first / max_entries int32 [T]
+        (uint32 bits); ent None: T = 0."""
+        if ent is None:
+            return DynTables(None, None, None, None, None, 0)
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        return DynTables(opt(tab_data), opt(tab_off), ent.data_ptr(),
+                         first.data_ptr(), max_entries.data_ptr(),
+                         first.numel())
+
+    def scan_headers_tabs(self, buf, sec_off, tabs, sec_tab, sec_win,
+                          max_hdrs, stream=None):
+        """qhuff_scan_headers_tabs on device tensors; tabs: a DynTables of
+        device pointers, sec_tab int32 [m] (None with T = 0), sec_win int32
+        [2m] or None -> as scan_headers_dyn."""
+        import torch
+        m = sec_off.numel() - 1
+        dev = buf.device
+        k = max(max_hdrs, 1)
+        strs = torch.empty(32 * k, dtype=torch.uint8, device=dev)
+        hdr_off = torch.empty(m + 1, dtype=torch.int32, device=dev)
+        rc = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        kind, sid, hf = (torch.empty(k, dtype=torch.uint8, device=dev)
+                         for _ in range(3))
+        did = torch.empty(k, dtype=torch.int32, device=dev)
+        self.scan_headers_tabs_into(buf, sec_off, m, tabs, sec_tab, sec_win,
+                                    strs, max_hdrs, hdr_off, rc, kind, sid,
+                                    hf, did, stream)
+        return strs, hdr_off, rc[:m], kind, sid, hf, did
+
+    def scan_headers_tabs_into(self, buf, sec_off, m, tabs, sec_tab, sec_win,
+                               strs, max_hdrs, hdr_off, rc, kind=None,
+                               static_id=None, hflags=None, dyn_id=None,
+                               stream=None):
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        r = lib().qhuff_scan_headers_tabs(
+            self._ctx, buf.data_ptr(), sec_off.data_ptr(), m, C.byref(tabs),
+            opt(sec_tab), opt(sec_win), opt(strs), max_hdrs,
+            hdr_off.data_ptr(), rc.data_ptr(), opt(kind), opt(static_id),
+            opt(hflags), opt(dyn_id), self._stream(stream))
+        self._check(r, "qhuff_scan_headers_tabs")
+
+    def scan_headers_tabs_host(self, buf, sec_off, tables, sec_tab,
+                               sec_win=None, max_hdrs=None):
+        """qhuff_scan_headers_tabs_host over host arrays -> as
+        scan_headers_tabs_cpu."""
+        import numpy as np
+        if max_hdrs is None:
+            max_hdrs = int(self.scan_headers_tabs_host(
+                buf, sec_off, tables, sec_tab, sec_win, 0)[2][-1])
+        buf, sec_off, m, strs, hdr_off, rc, kind, sid, hf = \
+            _headers_host_args(buf, sec_off, max_hdrs)
+        did = np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+        t, keep = dyn_tables_host(*(tables or ()))
+        tab, win = _opt_u32(sec_tab), _sec_win_host(sec_win)
+        ret = lib().qhuff_scan_headers_tabs_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, C.byref(t), _opt_ptr(tab),
+            _np_ptr(win) if win is not None else None, _np_ptr(strs),
+            max_hdrs, _np_ptr(hdr_off), _np_ptr(rc), _np_ptr(kind),
+            _np_ptr(sid), _np_ptr(hf), _np_ptr(did))
+        del keep
+        if ret not in (ERANGE, EINVAL):
+            self._check(ret, "qhuff_scan_headers_tabs_host")
+        n = min(int(hdr_off[-1]), max_hdrs)
+        return (ret, strs[:32 * n], hdr_off, rc[:m], kind[:n], sid[:n],
+                hf[:n], did[:n])
+
+    def decode_headers_tabs_host(self, buf, sec_off, tables, sec_tab,
+                                 sec_win=None, max_len=None, max_hdrs=None,
+                                 hashes=False):
+        """qhuff_decode_headers_tabs_host: scan and decode against a table
+        per section in one call -> as decode_headers_dyn_host (EINVAL / ERANGE
+        of the argument checks: the arrays after rc None)."""
+        import numpy as np
+        if max_hdrs is None:
+            max_hdrs = int(self.scan_headers_tabs_host(
+                buf, sec_off, tables, sec_tab, sec_win, 0)[2][-1])
+        buf, sec_off, m, _, hdr_off, rc, kind, sid, hf = \
+            _headers_host_args(buf, sec_off, max_hdrs)
+        did = np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+        t, keep = dyn_tables_host(*(tables or ()))
+        tab, win = _opt_u32(sec_tab), _sec_win_host(sec_win)
+        wire = max(int(sec_off[-1]) - int(sec_off[0]), 0)
+        out = np.zeros(decode_headers_dyn_bound(
+            wire, max_hdrs, _tabs_longest(tables or ())), dtype=np.uint8)
+        off = np.zeros(2 * max_hdrs + 1, dtype=np.uint32)
+        status = np.zeros(max(2 * max_hdrs, 1), dtype=np.uint8)
+        h1, h2 = (np.zeros(max(max_hdrs, 1), dtype=np.uint32)
+                  for _ in range(2))
+        ret = lib().qhuff_decode_headers_tabs_host(
+            self._ctx, _np_ptr(buf) if len(buf) else None, _np_ptr(sec_off),
+            m, C.byref(t), _opt_ptr(tab),
+            _np_ptr(win) if win is not None else None, max_len or 0, max_hdrs,
+            _np_ptr(hdr_off), _np_ptr(rc), _np_ptr(kind), _np_ptr(sid),
+            _np_ptr(hf), _np_ptr(did), _np_ptr(out), _np_ptr(off),
+            _np_ptr(status), _np_ptr(h1) if hashes else None,
+            _np_ptr(h2) if hashes else None)
+        del keep
+        tail = (None,) * (9 if hashes else 7)
+        if ret in (ERANGE, EINVAL):
+            return (ret, hdr_off, rc[:m]) + tail
+        self._check(ret, "qhuff_decode_headers_tabs_host")
+        n = int(hdr_off[-1])
+        res = (ret, hdr_off, rc[:m], kind[:n], sid[:n], hf[:n], did[:n],
+               out[:off[2 * n]], off[:2 * n + 1], status[:2 * n])
+        return res + ((h1[:n], h2[:n]) if hashes else ())
+
+    def dyn_lookup_tabs_into(self, data, off, n, sec_hdr, m, tabs, sec_tab,
+                             sec_win, name_hash, nameval_hash, kind,
+                             static_id, dyn_id=None, stream=None):
+        """qhuff_dyn_lookup_tabs on device tensors; tabs: a DynTables of
+        device pointers.  The form of the arrays is the caller's duty."""
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        rc = lib().qhuff_dyn_lookup_tabs(
+            self._ctx, data.data_ptr(), off.data_ptr(), n, sec_hdr.data_ptr(),
+            m, C.byref(tabs), opt(sec_tab), opt(sec_win), opt(name_hash),
+            opt(nameval_hash), kind.data_ptr(), static_id.data_ptr(),
+            opt(dyn_id), self._stream(stream))
+        self._check(rc, "qhuff_dyn_lookup_tabs")
+
+    def dyn_lookup_tabs(self, data, off, sec_hdr, tabs, sec_tab, sec_win=None,
+                        stream=None):
+        """-> (name_hash, nameval_hash int32 [n] (uint32 bits), kind,
+        static_id uint8 [n], dyn_id int32 [n] (uint32 bits))."""
+        import torch
+        n, m = (off.numel() - 1) // 2, sec_hdr.numel() - 1
+        h1, h2, did = (torch.empty(max(n, 1), dtype=torch.int32,
+                                   device=data.device) for _ in range(3))
+        kind, sid = (torch.empty(max(n, 1), dtype=torch.uint8,
+                                 device=data.device) for _ in range(2))
+        self.dyn_lookup_tabs_into(data, off, n, sec_hdr, m, tabs, sec_tab,
+                                  sec_win, h1, h2, kind, sid, did, stream)
+        return h1[:n], h2[:n], kind[:n], sid[:n], did[:n]
+
+    def dyn_lookup_tabs_host(self, data, off, sec_hdr, tables, sec_tab,
+                             sec_win=None):
+        """qhuff_dyn_lookup_tabs_host over host buffers -> as
+        dyn_lookup_tabs_cpu."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        sec_hdr = np.ascontiguousarray(sec_hdr, dtype=np.uint32)
+        n, m = (len(off) - 1) // 2, len(sec_hdr) - 1
+        h1, h2, did = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+        t, keep = dyn_tables_host(*(tables or ()))
+        tab, win = _opt_u32(sec_tab), _sec_win_host(sec_win)
+        ret = lib().qhuff_dyn_lookup_tabs_host(
+            self._ctx, _np_ptr(data) if len(data) else None, _np_ptr(off), n,
+            _np_ptr(sec_hdr), m, C.byref(t), _opt_ptr(tab), _opt_ptr(win),
+            _np_ptr(h1), _np_ptr(h2), _np_ptr(kind), _np_ptr(sid),
+            _np_ptr(did))
+        del keep
+        if ret not in (EINVAL, ERANGE):
+            self._check(ret, "qhuff_dyn_lookup_tabs_host")
+        return ret, h1[:n], h2[:n], kind[:n], sid[:n], did[:n]
+
+    def encode_headers_tabs_into(self, data, off, n, hflags, sec_hdr, m, tabs,
+                                 sec_tab, sec_win, sec_base, out, sec_out,
+                                 kind=None, static_id=None, dyn_id=None,
+                                 stream=None):
+        """qhuff_encode_headers_tabs on device tensors; tabs: a DynTables of
+        device pointers.  The form of the arrays is the caller's duty."""
+        opt = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        rc = lib().qhuff_encode_headers_tabs(
+            self._ctx, data.data_ptr(), off.data_ptr(), n, opt(hflags),
+            sec_hdr.data_ptr(), m, C.byref(tabs), opt(sec_tab), opt(sec_win),
+            opt(sec_base), out.data_ptr(), sec_out.data_ptr(), opt(kind),
+            opt(static_id), opt(dyn_id), self._stream(stream))
+        self._check(rc, "qhuff_encode_headers_tabs")
+
+    def encode_headers_tabs(self, data, off, sec_hdr, tabs, sec_tab,
+                            sec_win=None, sec_base=None, hflags=None,
+                            stream=None):
+        """-> (out uint8 [bound], sec_out int32 [m+1], kind, static_id uint8
+        [n], dyn_id int32 [n])."""
+        import torch
+        n, m = (off.numel() - 1) // 2, sec_hdr.numel() - 1
+        out = torch.empty(encode_headers_bound(int(data.numel()), n, m),
+                          dtype=torch.uint8, device=data.device)
+        sec_out = torch.empty(m + 1, dtype=torch.int32, device=data.device)
+        kind, sid = (torch.empty(max(n, 1), dtype=torch.uint8,
+                                 device=data.device) for _ in range(2))
+        did = torch.empty(max(n, 1), dtype=torch.int32, device=data.device)
+        self.encode_headers_tabs_into(data, off, n, hflags, sec_hdr, m, tabs,
+                                      sec_tab, sec_win, sec_base, out,
+                                      sec_out, kind, sid, did, stream)
+        return out, sec_out, kind[:n], sid[:n], did[:n]
+
+    def encode_headers_tabs_host(self, data, off, sec_hdr, tables, sec_tab,
+                                 sec_win=None, sec_base=None, hflags=None):
+        """qhuff_encode_headers_tabs_host over host buffers -> as
+        encode_headers_dyn_host."""
+        import numpy as np
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        sec_hdr = np.ascontiguousarray(sec_hdr, dtype=np.uint32)
+        if hflags is not None:
+            hflags = np.ascontiguousarray(hflags, dtype=np.uint8)
+        n, m = (len(off) - 1) // 2, len(sec_hdr) - 1
+        span = max(int(off[-1]) - int(off[0]), 0)
+        out = np.zeros(encode_headers_bound(span, n, m), dtype=np.uint8)
+        sec_out = np.zeros(m + 1, dtype=np.uint32)
+        kind, sid = (np.zeros(max(n, 1), dtype=np.uint8) for _ in range(2))
+        did = np.zeros(max(n, 1), dtype=np.uint32)
+        t, keep = dyn_tables_host(*(tables or ()))
+        tab, win = _opt_u32(sec_tab), _sec_win_host(sec_win)
+        base = _opt_u32(sec_base)
+        ret = lib().qhuff_encode_headers_tabs_host(
+            self._ctx, _np_ptr(data) if len(data) else None, _np_ptr(off), n,
+            _np_ptr(hflags) if hflags is not None and n else None,
+            _np_ptr(sec_hdr), m, C.byref(t), _opt_ptr(tab), _opt_ptr(win),
+            _opt_ptr(base), _np_ptr(out), _np_ptr(sec_out), _np_ptr(kind),
+            _np_ptr(sid), _np_ptr(did))
+        del keep
+        if ret in (EINVAL, ERANGE):
+            return ret, out[:0], sec_out, kind[:n], sid[:n], did[:n]
+        self._check(ret, "qhuff_encode_headers_tabs_host")
+        return ret, out[:sec_out[-1]], sec_out, kind[:n], sid[:n], did[:n]
 
     # host-memory batch calls (numpy) ----------------------------------------
     def encode_host(self, data, in_off, mode=ENC_PAYLOAD, out=None,
