@@ -989,7 +989,8 @@ int qhuff_decode_headers_host(qhuff_ctx *ctx, const uint8_t *buf,
  * each dynamic line to an entry (qdec_get_table_entry_abs, lsqpack.c:
  * 2768-2775) and copies name and value out (header_out_dynamic_entry,
  * 3060-3117; header_out_begin_dynamic_nameref, from 3655-3662); inserts come
- * only from the encoder stream (4544 ff.), which stays with the host.  With
+ * only from the encoder stream (4544 ff.), which these calls leave to the
+ * caller (qhuff_tabs_insert_host below applies it to a set of tables).  With
  * the entries at hand a dynamic line is per line and stateless, as a static
  * one is.  QHUFF_FEATURE_DECODE_HEADERS_DYN and the symbols announce it (the
  * ABI version is unchanged); the calls above behave as before.
@@ -1460,6 +1461,184 @@ int qhuff_encode_headers_tabs_host(qhuff_ctx *ctx, const uint8_t *in,
                                    const uint32_t *sec_base, uint8_t *out,
                                    uint32_t *sec_out, uint8_t *kind,
                                    uint8_t *static_id, uint32_t *dyn_id);
+
+/* ---- encoder-stream inserts applied to the connections' tables --------------
+ * The _tabs calls read a set of tables; these calls make the next one.  Chunk
+ * c, buf[enc_off[c] .. enc_off[c + 1]), is encoder-stream bytes of connection
+ * c (one chunk a table, T chunks); its complete instructions are applied to
+ * table c in order, as lsqpack_dec_enc_in does (lsqpack.c:4574-5030), and the
+ * T tables that result are written as a new arena, directly a struct
+ * qhuff_dyn_tables for the calls above.  A partial last instruction is left
+ * unconsumed, as by qhuff_scan_encoder_stream.  QHUFF_FEATURE_TABS_INSERT and
+ * the symbols announce it (the ABI version is unchanged); no call above
+ * changes.  The decoder stream, which blocked sections to submit again and
+ * everything the encoder decides stay with the host.
+ *
+ * State of table c: (cap, lo, ins, used) -- cap the capacity in bytes now in
+ * force (qpd_cur_max_capacity), lo the oldest live absolute index, ins the
+ * insert count (first[c] + d_c on entry), used the sum of name + value + 32
+ * over [lo, ins) (DTE_SIZE, qpd_cur_capacity).  struct qhuff_ins_state gives
+ * cap[T], max_cap[T] (qpd_max_capacity) and live_lo[T]; entries of the set
+ * below live_lo[c] are history kept for sections decoded earlier.
+ *
+ * Rules, the reference's, on complete instructions only (the reference can
+ * reject a partial one early by its declared length or index; here the
+ * verdict waits for the whole instruction -- a stated difference):
+ *   Set Dynamic Table Capacity v   v > max_cap[c] fails (lsqpack.c:5015);
+ *       else cap = v and entries are evicted from lo while used > cap
+ *       (qdec_update_max_capacity, 4362-4377).
+ *   Insert With Name Reference, static   index >= 99 fails (4620-4623).
+ *   Insert With Name Reference, dynamic, and Duplicate   a = ins - 1 - idx in
+ *       64 bits; fails unless lo <= a < ins at that moment
+ *       (qdec_get_table_entry_rel, 2756-2764; 4627-4630, 4987-4989): after
+ *       the evictions of the chunk's earlier instructions, before this
+ *       insert's own.  a may be an entry inserted earlier in the same chunk.
+ *   Lengths, on wire lengths, in 64 bits   a literal name of wire length Ln
+ *       with H bit Hn fails when Ln > cap << 2 * Hn (4798); with N the decoded
+ *       name's length, whatever its source, N > cap fails (4661, 4878), and
+ *       the value's wire length Lv fails when Lv > (cap - N) << 2 * Hv (4666,
+ *       4883).  A Duplicate has no such check.
+ *   A literal the Huffman decoder rejects fails.
+ *   Push (lsqpack_dec_push_entry, 4534-4552)   ins += 1, used += size, then
+ *       entries are evicted from lo while used > cap.  An entry that passed
+ *       the checks above but is larger than cap evicts everything, itself
+ *       included (lo = ins, used = 0), and is not an error.  RFC 9204 3.2.2
+ *       calls that an error; the reference is the definition here.
+ *   rc[c] = QHUFF_OK or QHUFF_EPROTO (the reference's -1).  A chunk that fails
+ *       changes nothing: its table comes out as it went in, no entry of it is
+ *       inserted and consumed[c] = 0; other chunks are unaffected.
+ * References are absolute indices where the reference's modular ids would
+ * alias, as in the calls above.
+ *
+ * Per chunk:   rc[T], consumed[T], ins_off[T + 1] -- the inserts of chunk c
+ *   are the ordinals [ins_off[c], ins_off[c + 1]); ins_off[T] is the full
+ *   count whatever max_ins is.  The ordinals are given out by the scan, before
+ *   anything is decoded: a chunk the scan rejects (an integer, a static index,
+ *   a capacity, Ln) has none; one rejected later (liveness, N, Lv, Huffman)
+ *   keeps its ordinals, with ins_lo[k] = live_lo[c] for each.
+ * Per insert k: ins_kind[k] = QHUFF_INS_*; ins_ref[k] = the absolute index
+ *   named, or QHUFF_DYN_NONE (also for an idx past the first insert);
+ *   ins_lo[k] = the oldest live absolute index right after insert k and its
+ *   evictions: a section decoded between inserts k and k + 1 has sec_win =
+ *   (ins_lo[k], first[c] + d_c + (k - ins_off[c]) + 1).
+ * The next set:  out_bytes, out_off[2D' + 1], out_ent[T + 1], out_first[T],
+ *   cap_out[T], live_lo_out[T]; cap_out and live_lo_out include the chunk's
+ *   trailing Set Capacity instructions.  Entry out_ent[c] + k has the
+ *   absolute index out_first[c] + k.  keep[T] (or NULL) is the lowest
+ *   absolute index to retain, clamped into [first[c], live_lo_out[c]]; NULL
+ *   retains exactly the live entries.  An empty table holds no bytes.
+ *   out_bytes must hold qhuff_tabs_insert_bound(arena_bytes, wire_bytes,
+ *   max_ins, dyn_longest) = arena_bytes + qhuff_decode_headers_dyn_bound(
+ *   wire_bytes, max_ins, dyn_longest) bytes -- the old arena plus everything
+ *   the inserts can decode to --, out_off 2 * (D + max_ins) + 1 entries.
+ *
+ * struct qhuff_ins_scan is what the scan leaves for the apply: the per-chunk
+ * and per-insert arrays above, chunk_cap[2T] (the minimum and the last
+ * capacity behind a chunk's last insert), two struct qhuff_hstr per insert
+ * (name, value) under the order rule -- WIRE for a literal, STATIC for a
+ * static name, DYN for a name or a duplicate taken from an entry of the input
+ * set -- root[2 * max_ins] and ins_cap[2 * max_ins] (the minimum capacity
+ * since the previous insert and the capacity in force).  A reference to an
+ * insert of the same chunk cannot be sized before decoding: it is a DYN
+ * descriptor of length 0 and root[] names the string of the same chunk whose
+ * bytes it takes (chains collapsed; QHUFF_DYN_NONE: the string's own).
+ *
+ * qhuff_scan_inserts_tabs: device pointers, asynchronous: the scan's three
+ *   launches on the scan's scratch (QHUFF_KIND_SCAN).  The caller reads
+ *   ins_off[T].
+ * qhuff_apply_inserts_tabs: device pointers, asynchronous; n_ins = ins_off[T]
+ *   (<= max_ins), wire_bytes = enc_off[T] - enc_off[0]: qhuff_decode_headers_
+ *   dyn's launch unchanged on the descriptors (max_len 0), the accounting (a
+ *   table a lane), the sums, the copy (a table a wave), the last three timed
+ *   as QHUFF_KIND_SCAN.  Scratch belongs to the context.  st->arena_bytes = the bytes of tabs->bytes (>= off[2D]),
+ *   st->dyn_longest >= the longest entry, o->out_cap / o->ent_cap = what
+ *   out_bytes / out_off hold: nothing is written past them.  The form of the
+ *   arrays is THE CALLER'S DUTY; what the kernels read of ent, off, enc_off,
+ *   live_lo, keep, root and the scan's arrays is clamped, so wrong arrays give
+ *   wrong bytes and no access outside the arrays -- with one value trusted,
+ *   as by the _tabs kernels above: D = ent[T], which the kernels read on the
+ *   device and clamp everything else to; off must hold 2 * ent[T] + 1
+ *   entries.
+ * qhuff_tabs_insert_host: host pointers, synchronous, the whole path: wire
+ *   bytes and tables go up once.  sc->strs, root, ins_cap, chunk_cap may be
+ *   NULL.  QHUFF_EINVAL unless first[c] <= live_lo[c] <= first[c] + d_c, used
+ *   <= cap[c] <= max_cap[c] <= 2^28 and max_entries[c] == max_cap[c] / 32 (and
+ *   for what tabs_check rejects, a decreasing enc_off, a null pointer);
+ *   QHUFF_ERANGE when ins_off[T] > max_ins (rc, consumed and ins_off valid,
+ *   nothing applied, the tables not written), when first + d + inserts
+ *   passes 2^32 - 1 or an arena passes 32 bits.
+ * qhuff_tabs_insert_cpu: the same shared source on the host, no context; its
+ *   literals are decoded by a host Huffman decoder of this library. */
+#define QHUFF_FEATURE_TABS_INSERT 1
+#define QHUFF_INS_LITERAL 0     /* insert with literal name                 */
+#define QHUFF_INS_STATIC  1     /* insert with static name reference        */
+#define QHUFF_INS_DYN     2     /* insert with dynamic name reference       */
+#define QHUFF_INS_DUP     3     /* duplicate                                */
+
+struct qhuff_ins_state {
+    const uint32_t *cap;        /* cap[T]                                   */
+    const uint32_t *max_cap;    /* max_cap[T]                               */
+    const uint32_t *live_lo;    /* live_lo[T]                               */
+    uint32_t arena_bytes;       /* device forms: bytes of tabs->bytes       */
+    uint32_t dyn_longest;       /* device forms: >= the longest entry       */
+};
+
+struct qhuff_ins_scan {
+    int32_t  *rc;               /* T                                        */
+    uint32_t *consumed;         /* T                                        */
+    uint32_t *ins_off;          /* T + 1                                    */
+    uint32_t *chunk_cap;        /* 2T                                       */
+    struct qhuff_hstr *strs;    /* 2 * max_ins                              */
+    uint32_t *root;             /* 2 * max_ins                              */
+    uint32_t *ins_cap;          /* 2 * max_ins                              */
+    uint32_t *ins_ref;          /* max_ins                                  */
+    uint8_t  *ins_kind;         /* max_ins                                  */
+    uint32_t max_ins;
+};
+
+struct qhuff_ins_out {
+    uint32_t *ins_lo;           /* max_ins                                  */
+    uint8_t  *out_bytes;
+    uint32_t *out_off;          /* 2 * ent_cap + 1                          */
+    uint32_t *out_ent;          /* T + 1                                    */
+    uint32_t *out_first;        /* T                                        */
+    uint32_t *cap_out;          /* T                                        */
+    uint32_t *live_lo_out;      /* T                                        */
+    uint64_t out_cap;           /* bytes out_bytes holds                    */
+    uint32_t ent_cap;           /* entries out_off holds (D + max_ins)      */
+};
+
+uint64_t qhuff_tabs_insert_bound(uint64_t arena_bytes, uint64_t wire_bytes,
+                                 uint32_t max_ins, uint32_t dyn_longest);
+
+int qhuff_scan_inserts_tabs(qhuff_ctx *ctx,
+                            const struct qhuff_dyn_tables *tabs,
+                            const struct qhuff_ins_state *st,
+                            const uint8_t *buf, const uint32_t *enc_off,
+                            const struct qhuff_ins_scan *sc, void *stream);
+
+int qhuff_apply_inserts_tabs(qhuff_ctx *ctx,
+                             const struct qhuff_dyn_tables *tabs,
+                             const struct qhuff_ins_state *st,
+                             const uint8_t *buf, uint32_t wire_bytes,
+                             const uint32_t *keep,
+                             const struct qhuff_ins_scan *sc, uint32_t n_ins,
+                             const struct qhuff_ins_out *o, void *stream);
+
+int qhuff_tabs_insert_host(qhuff_ctx *ctx,
+                           const struct qhuff_dyn_tables *tabs,
+                           const struct qhuff_ins_state *st,
+                           const uint8_t *buf, const uint32_t *enc_off,
+                           const uint32_t *keep,
+                           const struct qhuff_ins_scan *sc,
+                           const struct qhuff_ins_out *o);
+
+int qhuff_tabs_insert_cpu(const struct qhuff_dyn_tables *tabs,
+                          const struct qhuff_ins_state *st,
+                          const uint8_t *buf, const uint32_t *enc_off,
+                          const uint32_t *keep,
+                          const struct qhuff_ins_scan *sc,
+                          const struct qhuff_ins_out *o);
 
 /* ---- encoder-side hook ---------------------------
  * lsqpack_enc_enc_str (lsqpack.c:839-876) for a string whose Huffman

@@ -138,6 +138,11 @@ struct qhuff_ctx
                                          // found at the first call
     uint32_t tabs_grid[2];               // the same of the lookup over a set
                                          // of tables (qhuff_lookup_tabs.hip)
+    // qhuff_apply_inserts_tabs' scratch (the decode launch's outputs, the
+    // final lengths, the plans and the sums), grown on demand; ordered across
+    // streams with scan_ws, by scan_ev
+    uint8_t *ins_ws;
+    uint64_t ins_ws_cap;                 // bytes it holds
     char err_msg[256];
 };
 

@@ -24,7 +24,9 @@
 #include "qhuff_lookup_dyn_impl.h"
 #include "qhuff_names.h"
 #include "qhuff_scan_impl.h"
+#include "qhuff_tables.h"
 #include "qhuff_tabs_impl.h"
+#include "qhuff_tabs_insert_impl.h"
 
 namespace {
 
@@ -731,6 +733,263 @@ qhuff_static_probe_tables(uint8_t name2id_plus_one[512],
     memcpy(name2id_plus_one, kStaticHost.name2id, 512);
     memcpy(nameval2id_plus_one, kStaticHost.nameval2id, 512);
     return QHUFF_OK;
+}
+
+// ---- encoder-stream inserts applied to a set of tables, on the host ---------
+//
+// qhuff_tabs_insert_host's path in plain C++: the kernels' walker
+// (qhuff_scan_impl.h walk_insert_stream), the descriptors decoded by a host
+// decoder -- a bit-by-bit canonical Huffman walk over the code lengths of
+// qhuff_tables.h --, then the kernels' accounting, sums and copy
+// (qhuff_tabs_insert_impl.h).
+
+namespace {
+
+namespace qi = qhuff::ins;
+
+// RFC 7541 Appendix B as a canonical code: per length the first code, the
+// count and the rank of its first symbol; the symbols in canonical order
+struct HostHuff
+{
+    uint32_t first[31], count[31], base[31];
+    uint16_t sorted[257];
+    HostHuff()
+    {
+        memset(count, 0, sizeof(count));
+        for (int s = 0; s < 257; ++s)
+            count[qhuff::kLen[s]]++;
+        uint32_t next = 0, rank = 0;
+        first[0] = base[0] = 0;
+        for (int L = 1; L <= 30; ++L)
+        {
+            next <<= 1;
+            first[L] = next;
+            base[L] = rank;
+            next += count[L];
+            rank += count[L];
+        }
+        uint32_t at[31];
+        memcpy(at, base, sizeof(at));
+        for (int s = 0; s < 257; ++s)
+            sorted[at[qhuff::kLen[s]]++] = (uint16_t) s;
+    }
+};
+
+// src[0 .. n) decoded into dst (room for 8 n / 5): its length, or -1 (the EOS
+// code in the data, padding of more than 7 bits or not all ones:
+// QHUFF_DEC_ERROR)
+int64_t
+huff_decode_host(const uint8_t *src, uint32_t n, uint8_t *dst)
+{
+    static const HostHuff h;
+    uint32_t code = 0, len = 0;
+    int64_t m = 0;
+    for (uint64_t b = 0; b < 8ull * n; ++b)
+    {
+        code = code << 1 | ((src[b >> 3] >> (7 - (b & 7))) & 1);
+        ++len;
+        if (h.count[len] && code - h.first[len] < h.count[len])
+        {
+            const uint32_t sym = h.sorted[h.base[len] + code - h.first[len]];
+            if (sym == 256)
+                return -1;
+            dst[m++] = (uint8_t) sym;
+            code = len = 0;
+        }
+        else if (len == 30)
+            return -1;
+    }
+    if (len > 7 || code != (1u << len) - 1)
+        return -1;
+    return m;
+}
+
+// qhuff_decode_headers_dyn's result for 2n descriptors with max_len = 0
+void
+decode_strs_host(const uint8_t *buf, const struct qhuff_hstr *strs, uint64_t n2,
+                 const uint8_t *dyn, uint32_t dyn_len, uint8_t *out,
+                 uint32_t *off, uint8_t *status)
+{
+    uint32_t at = 0;
+    off[0] = 0;
+    for (uint64_t s = 0; s < n2; ++s)
+    {
+        const struct qhuff_hstr &d = strs[s];
+        status[s] = QHUFF_DEC_OK;
+        if (d.source == QHUFF_HSTR_STATIC)
+        {
+            const uint32_t id = d.static_id < qhuff::kStaticNames
+                                    ? d.static_id : qhuff::kStaticNames - 1;
+            const bool val = d.kind == QHUFF_LIT_VALUE;
+            const uint32_t nl = kStaticHost.name_len[id];
+            const uint32_t l = val ? kStaticHost.val_len[id] : nl;
+            for (uint32_t k = 0; k < l; ++k)
+                out[at + k] = (uint8_t) kStaticHost.byte(kStaticHost.at[id],
+                                                         (val ? nl : 0) + k);
+            at += l;
+        }
+        else if (d.source == QHUFF_HSTR_DYN)
+        {
+            const uint32_t from = d.instr < dyn_len ? d.instr : dyn_len;
+            const uint32_t l = d.len < dyn_len - from ? d.len : dyn_len - from;
+            if (l)
+                memcpy(out + at, dyn + from, l);
+            at += l;
+        }
+        else if (d.huffman)
+        {
+            const int64_t l = huff_decode_host(buf + d.pos, d.len, out + at);
+            if (l < 0)
+                status[s] = QHUFF_DEC_ERROR;
+            else
+                at += (uint32_t) l;
+        }
+        else
+        {
+            if (d.len)
+                memcpy(out + at, buf + d.pos, d.len);
+            at += d.len;
+        }
+        off[s + 1] = at;
+    }
+}
+
+}  // namespace
+
+extern "C" uint64_t
+qhuff_tabs_insert_bound(uint64_t arena_bytes, uint64_t wire_bytes,
+                        uint32_t max_ins, uint32_t dyn_longest)
+{
+    return arena_bytes + qi::decode_bound(wire_bytes, max_ins, dyn_longest);
+}
+
+extern "C" int
+qhuff_tabs_insert_cpu(const struct qhuff_dyn_tables *tabs,
+                      const struct qhuff_ins_state *st, const uint8_t *buf,
+                      const uint32_t *enc_off, const uint32_t *keep,
+                      const struct qhuff_ins_scan *sc,
+                      const struct qhuff_ins_out *o)
+{
+    namespace qs = qhuff::scan;
+    uint32_t D, longest;
+    if (const int r = qi::check(tabs, st, buf, enc_off, sc, o, &D, &longest))
+        return r;
+    const uint32_t T = tabs->T;
+    const uint64_t wire = T ? (uint64_t) enc_off[T] - enc_off[0] : 0;
+    const uint64_t arena = D ? tabs->off[2ull * D] : 0;
+    if (qhuff_tabs_insert_bound(arena, wire, sc->max_ins, longest)
+            > 0xffffffffull)
+        return QHUFF_ERANGE;
+    HostReader r{buf};
+    // the scan: the count pass, then the write pass
+    uint32_t *ccap = sc->chunk_cap ? sc->chunk_cap
+                                   : new uint32_t[2ull * T + 1];
+    sc->ins_off[0] = 0;
+    for (uint32_t c = 0; c < T; ++c)
+    {
+        qs::InsCountSink s{0, st->cap[c], st->cap[c]};
+        uint32_t stop = enc_off[c];
+        const int rc = qs::walk_insert_stream(r, s, enc_off[c], enc_off[c + 1],
+                                              st->cap[c], st->max_cap[c],
+                                              &stop);
+        sc->rc[c] = rc ? QHUFF_EPROTO : QHUFF_OK;
+        sc->consumed[c] = rc ? 0 : stop - enc_off[c];
+        ccap[2ull * c] = rc ? st->cap[c] : s.cmin;
+        ccap[2ull * c + 1] = rc ? st->cap[c] : s.cap;
+        sc->ins_off[c + 1] = sc->ins_off[c] + (rc ? 0 : s.n);
+    }
+    const uint32_t total = sc->ins_off[T];
+    int ret = total > sc->max_ins ? QHUFF_ERANGE
+                                  : qi::check_counts(tabs, sc->ins_off);
+    // (QHUFF_ERANGE: the first max_ins inserts' scan results, nothing applied)
+    const uint64_t n = total < sc->max_ins ? total : sc->max_ins;
+    struct qhuff_hstr *strs = sc->strs ? sc->strs
+                                       : new struct qhuff_hstr[2 * n + 1];
+    uint32_t *root = sc->root ? sc->root : new uint32_t[2 * n + 1];
+    uint32_t *icap = sc->ins_cap ? sc->ins_cap : new uint32_t[2 * n + 1];
+    uint32_t *dec_off = new uint32_t[2 * n + 1];
+    uint32_t *fin = new uint32_t[4 * n + 1], *rel = fin + 2 * n;
+    uint32_t *plan = new uint32_t[4ull * T + 1];
+    uint64_t *sums = new uint64_t[2ull * T + 2];
+    uint8_t *status = new uint8_t[2 * n + 1];
+    uint8_t *dec = nullptr;
+    for (uint32_t c = 0; c < T; ++c)
+    {
+        const uint32_t k0 = sc->ins_off[c];
+        const uint32_t k1 = sc->ins_off[c + 1] < n ? sc->ins_off[c + 1]
+                                                   : (uint32_t) n;
+        if (k0 >= k1)
+            continue;
+        const qs::TabView v = qs::ins_tab_view(tabs->ent, tabs->first, D, c);
+        qs::InsWriteSink w{strs, root, icap, sc->ins_ref, sc->ins_kind,
+                           tabs->off + 2ull * v.e0, v.d, v.first, k0, k0, k1};
+        uint32_t stop;
+        (void) qs::walk_insert_stream(r, w, enc_off[c], enc_off[c + 1],
+                                      st->cap[c], st->max_cap[c], &stop);
+    }
+    if (!ret)
+    {
+        dec = new uint8_t[qi::decode_bound(wire, (uint32_t) n, longest)];
+        decode_strs_host(buf, strs, 2 * n, tabs->bytes, (uint32_t) arena, dec,
+                         dec_off, status);
+        qi::Args a;
+        a.bytes = tabs->bytes;
+        a.off = tabs->off;
+        a.ent = tabs->ent;
+        a.first = tabs->first;
+        a.cap = st->cap;
+        a.live_lo = st->live_lo;
+        a.keep = keep;
+        a.T = T;
+        a.D = D;
+        a.arena = (uint32_t) arena;
+        a.rc = sc->rc;
+        a.consumed = sc->consumed;
+        a.ins_off = sc->ins_off;
+        a.chunk_cap = ccap;
+        a.strs = strs;
+        a.root = root;
+        a.ins_cap = icap;
+        a.ins_ref = sc->ins_ref;
+        a.ins_kind = sc->ins_kind;
+        a.n_ins = (uint32_t) n;
+        a.dec = dec;
+        a.dec_off = dec_off;
+        a.status = status;
+        a.fin = fin;
+        a.rel = rel;
+        a.plan = plan;
+        a.sums = sums;
+        a.ins_lo = o->ins_lo;
+        a.out_bytes = o->out_bytes;
+        a.out_off = o->out_off;
+        a.out_ent = o->out_ent;
+        a.out_first = o->out_first;
+        a.cap_out = o->cap_out;
+        a.live_lo_out = o->live_lo_out;
+        a.out_cap = o->out_cap;
+        a.ent_cap = o->ent_cap;
+        for (uint32_t c = 0; c < T; ++c)
+            qi::account(a, c);
+        qi::sums_host(a);
+        for (uint32_t c = 0; c < T; ++c)
+            qi::copy_host(a, c);
+    }
+    delete[] dec;
+    delete[] status;
+    delete[] sums;
+    delete[] plan;
+    delete[] fin;
+    delete[] dec_off;
+    if (icap != sc->ins_cap)
+        delete[] icap;
+    if (root != sc->root)
+        delete[] root;
+    if (strs != sc->strs)
+        delete[] strs;
+    if (ccap != sc->chunk_cap)
+        delete[] ccap;
+    return ret;
 }
 
 // ---- literal framing from a precomputed payload ---

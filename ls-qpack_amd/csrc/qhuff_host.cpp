@@ -3,6 +3,7 @@
 // device-pointer batch calls and host-only helpers (the rest: qhuff_ctx.h).
 #include "qhuff_ctx.h"
 #include "qhuff_lookup_dyn_impl.h"
+#include "qhuff_tabs_insert_impl.h"
 
 // ---------------------------------------------------------------------------
 // host side: context, C-ABI
@@ -408,6 +409,8 @@ qhuff_close(qhuff_ctx *c)
         (void) hipEventDestroy(c->hdr_ev);
     if (c->dyn_ws)
         (void) hipFree(c->dyn_ws);
+    if (c->ins_ws)
+        (void) hipFree(c->ins_ws);
     if (c->tev)
     {
         for (unsigned i = 0; i < 2 * QHUFF_TIMING_SLOTS; ++i)
@@ -2056,6 +2059,207 @@ qhuff_encode_headers_tabs(qhuff_ctx *c, const uint8_t *in, const uint32_t *off,
     return tabs_encode_dev(c, in, off, n, hflags, sec_hdr, m, tabs, D, sec_tab,
                            sec_win, sec_base, out, sec_out, kind, static_id,
                            dyn_id, st);
+}
+
+// ---- encoder-stream inserts applied to a set of tables -----------------------
+// (qhuff_insscan_tabs.hip, qhuff_insapply_tabs.hip)
+
+static inline size_t
+ins_up16(size_t x)
+{
+    return (x + 15) & ~(size_t) 15;
+}
+
+// the scan's frame over the insert walker: its scratch, its stream ordering,
+// its top launch
+extern "C" int
+qhuff_scan_inserts_tabs(qhuff_ctx *c, const struct qhuff_dyn_tables *tabs,
+                        const struct qhuff_ins_state *s, const uint8_t *buf,
+                        const uint32_t *enc_off,
+                        const struct qhuff_ins_scan *sc, void *stream)
+{
+    if (!c || !tabs || !s || !sc || !sc->ins_off)
+        return QHUFF_EINVAL;
+    const uint32_t T = tabs->T;
+    if (T && (!tabs->ent || !tabs->first || !tabs->off || !s->cap
+              || !s->max_cap || !buf || !enc_off || !sc->rc || !sc->consumed
+              || !sc->chunk_cap))
+        return QHUFF_EINVAL;
+    if (sc->max_ins && (!sc->strs || !sc->root || !sc->ins_cap || !sc->ins_ref
+                        || !sc->ins_kind))
+        return QHUFF_EINVAL;
+    if (sc->max_ins > 0x7fffffffu)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (T == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(sc->ins_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    if (const int r = scan_prepare(c, T, st))
+        return r;
+    InsScanArgs a;
+    a.buf = buf;
+    a.sec_off = enc_off;
+    a.off = tabs->off;
+    a.ent = tabs->ent;
+    a.first = tabs->first;
+    a.cap = s->cap;
+    a.max_cap = s->max_cap;
+    a.rc = sc->rc;
+    a.consumed = sc->consumed;
+    a.ins_off = sc->ins_off;
+    a.chunk_cap = sc->chunk_cap;
+    a.strs = sc->strs;
+    a.root = sc->root;
+    a.ins_cap = sc->ins_cap;
+    a.ins_ref = sc->ins_ref;
+    a.ins_kind = sc->ins_kind;
+    a.cnt = c->scan_ws;
+    a.tot = c->scan_ws + c->scan_cap;
+    a.m = T;
+    a.max_ins = sc->max_ins;
+    ScanArgs top = {};                   // (the top launch reads tot and m)
+    top.tot = a.tot;
+    top.m = T;
+    for (unsigned step = 0; step < 3; ++step)
+    {
+        const int r = timed(c, QHUFF_KIND_SCAN, "launch_insscan_tabs",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return step == 1 ? launch_scan(top, 1, st, e0, e1)
+                             : launch_insscan_tabs(a, step, st, e0, e1);
+        });
+        if (step || !r)
+        {
+            c->scan_stream = st;
+            c->scan_have = true;
+        }
+        if (r)
+            return r;
+    }
+    return QHUFF_OK;
+}
+
+// The decode launch on the scan's descriptors, then the accounting, the sums
+// and the copy, each timed as QHUFF_KIND_SCAN.  Scratch layout: [dec_off | fin
+// | rel | plan | sums | status | dec].
+extern "C" int
+qhuff_apply_inserts_tabs(qhuff_ctx *c, const struct qhuff_dyn_tables *tabs,
+                         const struct qhuff_ins_state *s, const uint8_t *buf,
+                         uint32_t wire_bytes, const uint32_t *keep,
+                         const struct qhuff_ins_scan *sc, uint32_t n_ins,
+                         const struct qhuff_ins_out *o, void *stream)
+{
+    if (!c || !tabs || !s || !sc || !o || !o->out_ent || !o->out_off
+            || !sc->ins_off)
+        return QHUFF_EINVAL;
+    const uint32_t T = tabs->T;
+    if (T && (!tabs->ent || !tabs->first || !tabs->off || !s->cap
+              || !s->live_lo || !sc->rc || !sc->consumed || !sc->chunk_cap
+              || !o->out_first || !o->cap_out || !o->live_lo_out
+              || (o->out_cap && !o->out_bytes)))
+        return QHUFF_EINVAL;
+    if (n_ins > sc->max_ins
+            || (n_ins && (!buf || !sc->strs || !sc->root || !sc->ins_cap
+                          || !sc->ins_ref || !sc->ins_kind || !o->ins_lo)))
+        return QHUFF_EINVAL;
+    const uint64_t bound = ins::decode_bound(wire_bytes, n_ins,
+                                             s->dyn_longest);
+    if (n_ins > 0x7fffffffu || bound > 0xffffffffull)
+        return QHUFF_ERANGE;
+    hipStream_t st = (hipStream_t) stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (T == 0)
+    {
+        HIPCHK(c, hipMemsetAsync(o->out_ent, 0, 4, st));
+        HIPCHK(c, hipMemsetAsync(o->out_off, 0, 4, st));
+        return QHUFF_OK;
+    }
+    if (const int r = scan_prepare(c, T, st))
+        return r;
+    const uint64_t n2 = 2ull * n_ins;
+    const size_t o_fin = ins_up16(4 * (n2 + 1));
+    const size_t o_rel = o_fin + ins_up16(4 * n2);
+    const size_t o_plan = o_rel + ins_up16(4 * n2);
+    const size_t o_sums = o_plan + 16ull * T;
+    const size_t o_st = o_sums + 16ull * (T + 1ull);
+    const size_t o_dec = o_st + ins_up16(n2);
+    const size_t need = o_dec + ins_up16(bound);
+    if (need > c->ins_ws_cap)
+    {
+        if (c->ins_ws)
+        {
+            // (earlier calls may still use it)
+            if (c->scan_have)
+                HIPCHK(c, hipStreamSynchronize(c->scan_stream));
+            HIPCHK(c, hipFree(c->ins_ws));
+            c->ins_ws = nullptr;
+            c->ins_ws_cap = 0;
+        }
+        const size_t cap = need < (1u << 20) ? (1u << 20) : need;
+        HIPCHK(c, hipMalloc((void **) &c->ins_ws, cap));
+        c->ins_ws_cap = cap;
+    }
+    uint8_t *W = c->ins_ws;
+    c->scan_stream = st;
+    c->scan_have = true;
+    if (n_ins)
+    {
+        const int r = qhuff_decode_headers_dyn(c, buf, sc->strs, n_ins, 0,
+                                               tabs->bytes, s->arena_bytes,
+                                               W + o_dec, (uint32_t *) W,
+                                               W + o_st, st);
+        if (r)
+            return r;
+    }
+    ins::Args a;
+    a.bytes = tabs->bytes;
+    a.off = tabs->off;
+    a.ent = tabs->ent;
+    a.first = tabs->first;
+    a.cap = s->cap;
+    a.live_lo = s->live_lo;
+    a.keep = keep;
+    a.T = T;
+    a.D = 0;                             // (the kernels read ent[T])
+    a.arena = s->arena_bytes;
+    a.rc = sc->rc;
+    a.consumed = sc->consumed;
+    a.ins_off = sc->ins_off;
+    a.chunk_cap = sc->chunk_cap;
+    a.strs = sc->strs;
+    a.root = sc->root;
+    a.ins_cap = sc->ins_cap;
+    a.ins_ref = sc->ins_ref;
+    a.ins_kind = sc->ins_kind;
+    a.n_ins = n_ins;
+    a.dec = W + o_dec;
+    a.dec_off = (const uint32_t *) W;
+    a.status = W + o_st;
+    a.fin = (uint32_t *) (W + o_fin);
+    a.rel = (uint32_t *) (W + o_rel);
+    a.plan = (uint32_t *) (W + o_plan);
+    a.sums = (uint64_t *) (W + o_sums);
+    a.ins_lo = o->ins_lo;
+    a.out_bytes = o->out_bytes;
+    a.out_off = o->out_off;
+    a.out_ent = o->out_ent;
+    a.out_first = o->out_first;
+    a.cap_out = o->cap_out;
+    a.live_lo_out = o->live_lo_out;
+    a.out_cap = o->out_cap;
+    a.ent_cap = o->ent_cap;
+    for (unsigned step = 0; step < 3; ++step)
+    {
+        const int r = timed(c, QHUFF_KIND_SCAN, "launch_insapply_tabs",
+                            [&](hipEvent_t e0, hipEvent_t e1) {
+            return launch_insapply_tabs(a, step, st, e0, e1);
+        });
+        if (r)
+            return r;
+    }
+    return QHUFF_OK;
 }
 
 // ---- host helpers --------------------------------------------------------------

@@ -1,6 +1,7 @@
 // qhuff_hostpath.cpp -- the pinned host-memory path of the C-ABI, buffer
 // registration and the per-string mirrors of the reference entry points.
 #include "qhuff_ctx.h"
+#include "qhuff_tabs_insert_impl.h"
 #include "qhuff_scan_impl.h"
 #include "qhuff_lookup_dyn_impl.h"
 #include "qhuff_tabs_impl.h"
@@ -2131,6 +2132,182 @@ qhuff_decode_headers_tabs_host(qhuff_ctx *c, const uint8_t *buf,
             memcpy(name_hash, H + o_h1, 4ull * n);
         if (nameval_hash)
             memcpy(nameval_hash, H + o_h2, 4ull * n);
+    }
+    return QHUFF_OK;
+}
+
+// ---- encoder-stream inserts applied to a set of tables, host buffers ---------
+
+// The whole path: the wire bytes, the set and its state go up once; the scan
+// runs and its small results come back (n = ins_off[T]); the apply runs on
+// the descriptors where they are; the per-insert arrays, the next set's small
+// arrays and offsets come back, then exactly its bytes.  Stage layout: [16 |
+// wire bytes | 16 | enc_off | the set (TabsUp) | cap | max_cap | live_lo | keep
+// | rc | consumed | ins_off | chunk_cap | ins_ref | ins_kind | strs | root |
+// ins_cap | ins_lo | out_ent | out_first | cap_out | live_lo_out | out_off |
+// out_bytes], the per-insert parts sized for max_ins.
+extern "C" int
+qhuff_tabs_insert_host(qhuff_ctx *c, const struct qhuff_dyn_tables *tabs,
+                       const struct qhuff_ins_state *s, const uint8_t *buf,
+                       const uint32_t *enc_off, const uint32_t *keep,
+                       const struct qhuff_ins_scan *sc,
+                       const struct qhuff_ins_out *o)
+{
+    if (!c)
+        return QHUFF_EINVAL;
+    uint32_t D_all, longest;
+    if (const int r = ins::check(tabs, s, buf, enc_off, sc, o, &D_all,
+                                 &longest))
+        return r;
+    const uint64_t T = tabs->T, mi = sc->max_ins;
+    if (T == 0)
+    {
+        sc->ins_off[0] = 0;
+        o->out_ent[0] = 0;
+        o->out_off[0] = 0;
+        return QHUFF_OK;
+    }
+    const uint64_t a0 = enc_off[0], wire = (uint64_t) enc_off[T] - a0;
+    const uint64_t arena = D_all ? tabs->off[2ull * D_all] : 0;
+    const uint64_t bound = qhuff_tabs_insert_bound(arena, wire, sc->max_ins,
+                                                   longest);
+    if (bound > 0xffffffffull || D_all + mi > 0x7fffffffull)
+        return QHUFF_ERANGE;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t o_eo = up16(16 + wire) + 16;
+    const TabsUp u = tabs_up(tabs, D_all, o_eo + up16(4 * (T + 1)));
+    const size_t o_cap = u.end;
+    const size_t o_mc = o_cap + up16(4 * T);
+    const size_t o_ll = o_mc + up16(4 * T);
+    const size_t o_keep = o_ll + up16(4 * T);
+    const size_t o_rc = o_keep + up16(keep ? 4 * T : 0);
+    const size_t o_cons = o_rc + up16(4 * T);
+    const size_t o_io = o_cons + up16(4 * T);
+    const size_t o_cc = o_io + up16(4 * (T + 1));
+    const size_t o_ref = o_cc + up16(8 * T);
+    const size_t o_kind = o_ref + up16(4 * mi);
+    const size_t o_strs = o_kind + up16(mi);
+    const size_t o_root = o_strs + 32 * mi;
+    const size_t o_icap = o_root + up16(8 * mi);
+    const size_t o_lo = o_icap + up16(8 * mi);
+    const size_t o_oe = o_lo + up16(4 * mi);
+    const size_t o_of = o_oe + up16(4 * (T + 1));
+    const size_t o_co = o_of + up16(4 * T);
+    const size_t o_lo2 = o_co + up16(4 * T);
+    const size_t o_oo = o_lo2 + up16(4 * T);
+    const size_t o_ob = o_oo + up16(4 * (2 * (D_all + mi) + 1));
+    int r = stage_up(c, o_ob + up16(bound),
+                     {{buf + a0, (size_t) wire, 16},
+                      {enc_off, (size_t) (4 * (T + 1)), o_eo},
+                      TABS_STAGE_IN(tabs, u),
+                      {s->cap, (size_t) (4 * T), o_cap},
+                      {s->max_cap, (size_t) (4 * T), o_mc},
+                      {s->live_lo, (size_t) (4 * T), o_ll},
+                      {keep, keep ? (size_t) (4 * T) : 0, o_keep}},
+                     o_rc);
+    if (r)
+        return r;
+    uint8_t *H = c->h_stage, *Dv = c->d_stage;
+    hipStream_t sk = c->own_stream;
+    const struct qhuff_dyn_tables dev = tabs_dev(tabs, u, Dv);
+    struct qhuff_ins_state ds;
+    ds.cap = (const uint32_t *) (Dv + o_cap);
+    ds.max_cap = (const uint32_t *) (Dv + o_mc);
+    ds.live_lo = (const uint32_t *) (Dv + o_ll);
+    ds.arena_bytes = (uint32_t) arena;
+    ds.dyn_longest = longest;
+    struct qhuff_ins_scan dsc;
+    dsc.rc = (int32_t *) (Dv + o_rc);
+    dsc.consumed = (uint32_t *) (Dv + o_cons);
+    dsc.ins_off = (uint32_t *) (Dv + o_io);
+    dsc.chunk_cap = (uint32_t *) (Dv + o_cc);
+    dsc.strs = (struct qhuff_hstr *) (Dv + o_strs);
+    dsc.root = (uint32_t *) (Dv + o_root);
+    dsc.ins_cap = (uint32_t *) (Dv + o_icap);
+    dsc.ins_ref = (uint32_t *) (Dv + o_ref);
+    dsc.ins_kind = Dv + o_kind;
+    dsc.max_ins = sc->max_ins;
+    r = qhuff_scan_inserts_tabs(c, &dev, &ds, Dv + 16 - a0,
+                                (const uint32_t *) (Dv + o_eo), &dsc, sk);
+    if (r)
+        return r;
+    HIPCHK(c, hipMemcpyAsync(H + o_rc, Dv + o_rc, o_ref - o_rc,
+                             hipMemcpyDeviceToHost, sk));
+    HIPCHK(c, hipStreamSynchronize(sk));
+    memcpy(sc->rc, H + o_rc, 4 * T);
+    memcpy(sc->consumed, H + o_cons, 4 * T);
+    memcpy(sc->ins_off, H + o_io, 4 * (T + 1));
+    if (sc->chunk_cap)
+        memcpy(sc->chunk_cap, H + o_cc, 8 * T);
+    const uint64_t total = sc->ins_off[T], n = total < mi ? total : mi;
+    auto scan_out = [&]() {
+        if (!n)
+            return;
+        memcpy(sc->ins_ref, H + o_ref, 4 * n);
+        memcpy(sc->ins_kind, H + o_kind, n);
+        if (sc->strs)
+            memcpy(sc->strs, H + o_strs, 32 * n);
+        if (sc->root)
+            memcpy(sc->root, H + o_root, 8 * n);
+        if (sc->ins_cap)
+            memcpy(sc->ins_cap, H + o_icap, 8 * n);
+    };
+    r = total > mi ? QHUFF_ERANGE : ins::check_counts(tabs, sc->ins_off);
+    if (r)
+    {
+        // (the scan's convention: the first max_ins inserts' scan results)
+        if (n)
+        {
+            HIPCHK(c, hipMemcpyAsync(H + o_ref, Dv + o_ref, o_lo - o_ref,
+                                     hipMemcpyDeviceToHost, sk));
+            HIPCHK(c, hipStreamSynchronize(sk));
+        }
+        scan_out();
+        return r;
+    }
+    struct qhuff_ins_out dout;
+    dout.ins_lo = (uint32_t *) (Dv + o_lo);
+    dout.out_bytes = Dv + o_ob;
+    dout.out_off = (uint32_t *) (Dv + o_oo);
+    dout.out_ent = (uint32_t *) (Dv + o_oe);
+    dout.out_first = (uint32_t *) (Dv + o_of);
+    dout.cap_out = (uint32_t *) (Dv + o_co);
+    dout.live_lo_out = (uint32_t *) (Dv + o_lo2);
+    dout.out_cap = bound;
+    dout.ent_cap = (uint32_t) (D_all + mi);
+    r = qhuff_apply_inserts_tabs(c, &dev, &ds, Dv + 16 - a0, (uint32_t) wire,
+                                 keep ? (const uint32_t *) (Dv + o_keep)
+                                      : nullptr,
+                                 &dsc, (uint32_t) n, &dout, sk);
+    if (r)
+        return r;
+    HIPCHK(c, hipMemcpyAsync(H + o_rc, Dv + o_rc, o_ob - o_rc,
+                             hipMemcpyDeviceToHost, sk));
+    HIPCHK(c, hipStreamSynchronize(sk));
+    if (const int e = mirror_error(c))
+        return e;
+    memcpy(sc->rc, H + o_rc, 4 * T);
+    memcpy(sc->consumed, H + o_cons, 4 * T);
+    scan_out();
+    if (n)
+        memcpy(o->ins_lo, H + o_lo, 4 * n);
+    memcpy(o->out_ent, H + o_oe, 4 * (T + 1));
+    memcpy(o->out_first, H + o_of, 4 * T);
+    memcpy(o->cap_out, H + o_co, 4 * T);
+    memcpy(o->live_lo_out, H + o_lo2, 4 * T);
+    const uint64_t De = o->out_ent[T];
+    if (De > o->ent_cap || De > D_all + mi)
+        return QHUFF_EINVAL;             // (out_off too small for the set)
+    memcpy(o->out_off, H + o_oo, 4 * (2 * De + 1));
+    const uint64_t bytes = o->out_off[2 * De];
+    if (bytes > o->out_cap)
+        return QHUFF_EINVAL;
+    if (bytes)
+    {
+        HIPCHK(c, hipMemcpyAsync(H + o_ob, Dv + o_ob, bytes,
+                                 hipMemcpyDeviceToHost, sk));
+        HIPCHK(c, hipStreamSynchronize(sk));
+        memcpy(o->out_bytes, H + o_ob, bytes);
     }
     return QHUFF_OK;
 }

@@ -217,6 +217,25 @@ struct TabsLookupArgs
     uint32_t T, D, mask;
 };
 
+// encoder-stream inserts of T connections walked on the device
+// (qhuff_insscan_tabs.hip): chunk c of buf between sec_off[c .. c + 1] against
+// table c of the set; the scan's scratch.  The kernels read D = ent[T].
+struct InsScanArgs
+{
+    const uint8_t *buf;
+    const uint32_t *sec_off;     // enc_off, T + 1
+    const uint32_t *off, *ent, *first;
+    const uint32_t *cap, *max_cap;
+    int32_t *rc;
+    uint32_t *consumed, *ins_off, *chunk_cap;
+    ::qhuff_hstr *strs;          // 2 * max_ins
+    uint32_t *root, *ins_cap;    // 2 * max_ins each
+    uint32_t *ins_ref;           // max_ins
+    uint8_t *ins_kind;           // max_ins
+    uint32_t *cnt, *tot;
+    uint32_t m, max_ins;         // m = T
+};
+
 // ---- low-latency service (qhuff_service.hip, qhuff_svc_host.cpp) ----------
 //
 // One request slot per service wave, in pinned host memory mapped into the
@@ -402,6 +421,17 @@ hipError_t launch_tabs_prefix(const TabsLookupArgs &a, hipStream_t st,
                               hipEvent_t ev0 = nullptr,
                               hipEvent_t ev1 = nullptr);
 hipError_t lookup_tabs_occupancy(bool enc, int *blocks_per_cu);
+// the inserts' scan (step 0 count, 2 write; its sums are launch_scan's step 1
+// over the same tot), m >= 1, and their apply (qhuff_insapply_tabs.hip;
+// ins::Args of qhuff_tabs_insert_impl.h, T >= 1): step 0 the accounting, 1
+// the sums, 2 the copy
+hipError_t launch_insscan_tabs(const InsScanArgs &a, unsigned step,
+                               hipStream_t st, hipEvent_t ev0 = nullptr,
+                               hipEvent_t ev1 = nullptr);
+namespace ins { struct Args; }
+hipError_t launch_insapply_tabs(const ins::Args &a, unsigned step,
+                                hipStream_t st, hipEvent_t ev0 = nullptr,
+                                hipEvent_t ev1 = nullptr);
 // m sections of no headers: out = m x "00 00", sec_out[s] = 2s, s in [0, m]
 hipError_t launch_empty_sections(uint32_t m, uint8_t *out, uint32_t *sec_out,
                                  hipStream_t st);

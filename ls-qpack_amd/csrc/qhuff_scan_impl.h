@@ -720,5 +720,192 @@ walk_header_section(R &r, S &s, uint32_t a, uint32_t b)
     return walk_header_section(r, s, a, b, NoDyn());
 }
 
+// ---- encoder-stream inserts (qhuff_scan_inserts_tabs) ------------------------
+//
+// walk_encoder_stream's four instructions walked for what they mean
+// (lsqpack_dec_enc_in, lsqpack.c:4574-5030): every insert goes to a sink with
+// the capacity it is checked and pushed under.  The capacity of a chunk is a
+// function of cap[c] and the chunk's Set Capacity instructions alone, so the
+// walk tracks it; what depends on decoded sizes -- the liveness of a
+// reference, N > cap, the value's length, the push -- is the accounting's
+// (qhuff_tabs_insert_impl.h).  A verdict is given on complete instructions.
+//
+// Sinks: insert(kind, idx, at, name, value, cmin, cap) takes the next insert
+// -- kind QHUFF_INS_*, idx its static or relative index, at its first byte,
+// cmin the lowest capacity since the previous insert (cap included), cap the
+// one in force; tail(cmin, cap): the same behind the last insert.
+struct InsCountSink
+{
+    uint32_t n, cmin, cap;
+    QH_HD void insert(uint32_t, uint32_t, uint32_t, const Lit &, const Lit &,
+                      uint32_t, uint32_t)
+    {
+        ++n;
+    }
+    QH_HD void tail(uint32_t m, uint32_t c)
+    {
+        cmin = m;
+        cap = c;
+    }
+};
+
+// Inserts with ordinals in [n0, limit) are written: two descriptors, two
+// roots, the two capacities, the reference and the kind.  off: the set's
+// offsets based at the table's first entry (d entries from the absolute index
+// first).  A reference to an insert of the same chunk is a DYN descriptor of
+// length 0 whose root is that insert's string, or that string's own root: the
+// lane reads back what it wrote itself, earlier in program order.
+struct InsWriteSink
+{
+    ::qhuff_hstr *strs;
+    uint32_t *root, *ins_cap, *ins_ref;
+    uint8_t *ins_kind;
+    const uint32_t *off;
+    uint32_t d, first;
+    uint32_t n0, n, limit;
+
+    QH_HD uint32_t root_of(uint64_t s) const
+    {
+        const uint32_t r = root[s];
+        return r == QHUFF_DYN_NONE ? (uint32_t) s : r;
+    }
+    QH_HD void insert(uint32_t kind, uint32_t idx, uint32_t at,
+                      const Lit &name, const Lit &value, uint32_t cmin,
+                      uint32_t cap)
+    {
+        if (n < limit)
+        {
+            const uint64_t i = 2 * (uint64_t) n;
+            const uint64_t ins0 = (uint64_t) first + d, ins = ins0 + (n - n0);
+            uint32_t ref = QHUFF_DYN_NONE, rn = QHUFF_DYN_NONE,
+                     rv = QHUFF_DYN_NONE;
+            ::qhuff_hstr sn, sv = hstr_wire(value, QHUFF_LIT_VALUE, at);
+            if (kind == QHUFF_INS_LITERAL)
+                sn = hstr_wire(name, QHUFF_LIT_NAME, at);
+            else if (kind == QHUFF_INS_STATIC)
+                sn = hstr_static(idx, QHUFF_LIT_NAME, at);
+            else
+            {
+                const bool dup = kind == QHUFF_INS_DUP;
+                sn = hstr_dyn(0, 0, QHUFF_LIT_NAME, at);
+                if (dup)
+                    sv = hstr_dyn(0, 0, QHUFF_LIT_VALUE, at);
+                if (idx < ins)
+                {
+                    const uint64_t a = ins - 1 - idx;
+                    ref = (uint32_t) a;
+                    if (a >= ins0)
+                    {
+                        // (a - ins0 < n - n0: an ordinal this lane wrote)
+                        const uint64_t k = 2 * (n0 + (a - ins0));
+                        rn = root_of(k);
+                        if (dup)
+                            rv = root_of(k + 1);
+                    }
+                    else if (a >= first)
+                    {
+                        const uint64_t e = 2 * (a - first);
+                        const uint32_t o0 = off[e], o1 = off[e + 1],
+                                       o2 = off[e + 2];
+                        sn = hstr_dyn(o0, o1 > o0 ? o1 - o0 : 0u,
+                                      QHUFF_LIT_NAME, at);
+                        if (dup)
+                            sv = hstr_dyn(o1, o2 > o1 ? o2 - o1 : 0u,
+                                          QHUFF_LIT_VALUE, at);
+                    }
+                }
+            }
+            strs[i] = sn;
+            strs[i + 1] = sv;
+            root[i] = rn;
+            root[i + 1] = rv;
+            ins_cap[i] = cmin;
+            ins_cap[i + 1] = cap;
+            ins_ref[n] = ref;
+            ins_kind[n] = (uint8_t) kind;
+        }
+        ++n;
+    }
+    QH_HD void tail(uint32_t, uint32_t) {}
+};
+
+// encoder-stream bytes in [p, end) of a table with capacity cap and maximum
+// max_cap: 0 with *stop the end of the last complete instruction, or -2
+template <class R, class S>
+QH_HD inline int
+walk_insert_stream(R &r, S &s, uint32_t p, uint32_t end, uint32_t cap,
+                   uint32_t max_cap, uint32_t *stop)
+{
+    uint32_t cmin = cap;
+    while (p < end)
+    {
+        uint32_t q = p;
+        const uint8_t b = r.get(q);
+        uint32_t idx = 0, kind;
+        LitCatch name, value;
+        name.l = Lit();
+        value.l = Lit();
+        int rc;
+        if (b & 0x80)                // 1Txxxxxx insert with name reference
+        {
+            kind = (b & 0x40) ? QHUFF_INS_STATIC : QHUFF_INS_DYN;
+            rc = dec_int24(r, &q, end, 6, &idx);
+            if (!rc)
+                rc = literal(r, value, &q, end, 7, QHUFF_LIT_VALUE, p, 0);
+            if (!rc && kind == QHUFF_INS_STATIC && idx >= kHdrStaticEntries)
+                rc = -2;                             // lsqpack.c:4620-4623
+        }
+        else if (b & 0x40)           // 01Hxxxxx insert with literal name
+        {
+            kind = QHUFF_INS_LITERAL;
+            rc = literal(r, name, &q, end, 5, QHUFF_LIT_NAME, p, 0);
+            if (!rc)
+                rc = literal(r, value, &q, end, 7, QHUFF_LIT_VALUE, p, 0);
+            if (!rc && name.l.len > ((uint64_t) cap << 2 * name.l.h))
+                rc = -2;                             // lsqpack.c:4798
+        }
+        else if (b & 0x20)           // 001xxxxx set dynamic table capacity
+        {
+            uint64_t w;
+            rc = dec_int(r, &q, end, 5, &w);
+            if (rc == -1)
+                break;
+            if (rc || w > max_cap)                   // lsqpack.c:5015
+                return -2;
+            cap = (uint32_t) w;
+            cmin = cap < cmin ? cap : cmin;
+            p = q;
+            continue;
+        }
+        else                         // 000xxxxx duplicate
+        {
+            kind = QHUFF_INS_DUP;
+            rc = dec_int24(r, &q, end, 5, &idx);
+        }
+        if (rc == -1)
+            break;
+        if (rc)
+            return rc;
+        s.insert(kind, idx, p, name.l, value.l, cmin, cap);
+        cmin = cap;
+        p = q;
+    }
+    *stop = p;
+    s.tail(cmin, cap);
+    return 0;
+}
+
+// the scan's view of table c of a set for its chunk: the entries' offsets
+// based at the table's first entry, d, first (tab_view's clamps)
+template <class P>
+QH_HD inline TabView
+ins_tab_view(P ent, P first, uint32_t D, uint32_t c)
+{
+    uint32_t e0 = ent[c], e1 = ent[c + 1];
+    e0 = e0 < D ? e0 : D;
+    e1 = e1 < D ? e1 : D;
+    return TabView{c, e0, e1 > e0 ? e1 - e0 : 0u, first[c], 0};
+}
+
 }  // namespace scan
 }  // namespace qhuff

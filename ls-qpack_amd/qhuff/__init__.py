@@ -69,6 +69,9 @@ EXPORTS = (
     "qhuff_dyn_lookup_tabs", "qhuff_dyn_lookup_tabs_host",
     "qhuff_dyn_lookup_tabs_cpu", "qhuff_dyn_tables_index_slots",
     "qhuff_encode_headers_tabs", "qhuff_encode_headers_tabs_host",
+    "qhuff_tabs_insert_bound", "qhuff_scan_inserts_tabs",
+    "qhuff_apply_inserts_tabs", "qhuff_tabs_insert_host",
+    "qhuff_tabs_insert_cpu",
     # include/qhuff_lsqpack.h
     "qhuff_lsqpack_enc_enc_str", "qhuff_lsqpack_huff_decode",
     "qhuff_lsqpack_set_decode_full", "qhuff_lsqpack_set_device",
@@ -80,6 +83,7 @@ EBLOCKED = -11                            # QHUFF_EBLOCKED (qhuff_scan_headers_d
 HSTR_WIRE, HSTR_STATIC, HSTR_DYN = 0, 1, 2    # QHUFF_HSTR_*
 LINE_DYN = 4                              # QHUFF_LINE_DYN
 DYN_NONE = 0xFFFFFFFF                     # QHUFF_DYN_NONE
+INS_LITERAL, INS_STATIC, INS_DYN, INS_DUP = 0, 1, 2, 3    # QHUFF_INS_*
 HSTR_WIRE, HSTR_STATIC = 0, 1             # QHUFF_HSTR_*
 TIMING_SLOTS = 256                        # QHUFF_TIMING_SLOTS
 KIND_ENCODE, KIND_DECODE, KIND_HASH = 0, 1, 2
@@ -470,6 +474,21 @@ def lib():
         L.qhuff_encode_headers_tabs_host.restype = C.c_int
         L.qhuff_encode_headers_tabs_host.argtypes = [vp, vp, vp, u32, vp, vp,
                                                      u32, tsp] + [vp] * 8
+        # (encoder-stream inserts applied to a set of tables)
+        isp, icp, iop = (C.POINTER(InsState), C.POINTER(InsScan),
+                         C.POINTER(InsOut))
+        L.qhuff_tabs_insert_bound.restype = C.c_uint64
+        L.qhuff_tabs_insert_bound.argtypes = [C.c_uint64, C.c_uint64, u32, u32]
+        L.qhuff_scan_inserts_tabs.restype = C.c_int
+        L.qhuff_scan_inserts_tabs.argtypes = [vp, tsp, isp, vp, vp, icp, vp]
+        L.qhuff_apply_inserts_tabs.restype = C.c_int
+        L.qhuff_apply_inserts_tabs.argtypes = [vp, tsp, isp, vp, u32, vp, icp,
+                                               u32, iop, vp]
+        L.qhuff_tabs_insert_host.restype = C.c_int
+        L.qhuff_tabs_insert_host.argtypes = [vp, tsp, isp, vp, vp, vp, icp,
+                                             iop]
+        L.qhuff_tabs_insert_cpu.restype = C.c_int
+        L.qhuff_tabs_insert_cpu.argtypes = [tsp, isp, vp, vp, vp, icp, iop]
         L.qhuff_decode_headers_host.restype = C.c_int
         L.qhuff_decode_headers_host.argtypes = [vp, vp, u32p, C.c_uint32,
                                                 C.c_uint32, C.c_uint32, u32p,
@@ -813,6 +832,127 @@ def dyn_lookup_tabs_cpu(data, off, sec_hdr, tables, sec_tab, sec_win=None):
         _np_ptr(did))
     del keep
     return ret, h1[:n], h2[:n], kind[:n], sid[:n], did[:n]
+
+
+# ---- encoder-stream inserts applied to a set of tables -----------------------
+
+class InsState(C.Structure):
+    """struct qhuff_ins_state"""
+    _fields_ = [("cap", C.c_void_p), ("max_cap", C.c_void_p),
+                ("live_lo", C.c_void_p), ("arena_bytes", C.c_uint32),
+                ("dyn_longest", C.c_uint32)]
+
+
+class InsScan(C.Structure):
+    """struct qhuff_ins_scan"""
+    _fields_ = [("rc", C.c_void_p), ("consumed", C.c_void_p),
+                ("ins_off", C.c_void_p), ("chunk_cap", C.c_void_p),
+                ("strs", C.c_void_p), ("root", C.c_void_p),
+                ("ins_cap", C.c_void_p), ("ins_ref", C.c_void_p),
+                ("ins_kind", C.c_void_p), ("max_ins", C.c_uint32)]
+
+
+class InsOut(C.Structure):
+    """struct qhuff_ins_out"""
+    _fields_ = [("ins_lo", C.c_void_p), ("out_bytes", C.c_void_p),
+                ("out_off", C.c_void_p), ("out_ent", C.c_void_p),
+                ("out_first", C.c_void_p), ("cap_out", C.c_void_p),
+                ("live_lo_out", C.c_void_p), ("out_cap", C.c_uint64),
+                ("ent_cap", C.c_uint32)]
+
+
+def tabs_insert_bound(arena_bytes, wire_bytes, max_ins, dyn_longest):
+    return int(lib().qhuff_tabs_insert_bound(arena_bytes, wire_bytes, max_ins,
+                                             dyn_longest))
+
+
+class Inserted:
+    """What an insert call gives: ret; per chunk rc, consumed, ins_off,
+    chunk_cap; per insert ins_kind, ins_ref, ins_lo, strs (the descriptors'
+    bytes), root, ins_cap; the next set as `tables` = (data, off, ent, first,
+    max_entries), the tuple the _tabs calls take, with cap and live_lo.  On
+    QHUFF_EINVAL nothing but ret is set; on QHUFF_ERANGE the next set is
+    None."""
+    tables = cap = live_lo = None
+
+
+def _tabs_insert(fn, ctx, what, tables, cap, max_cap, live_lo, buf, enc_off,
+                 keep, max_ins):
+    import numpy as np
+    u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)  # noqa: E731
+    cap, max_cap, live_lo = u32(cap), u32(max_cap), u32(live_lo)
+    enc_off = u32(enc_off)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    t, keep_t = dyn_tables_host(*(tables or ()))
+    T = t.T
+    D = int(keep_t[2][-1]) if T else 0
+    if max_ins is None:
+        max_ins = int(_tabs_insert(fn, ctx, what, tables, cap, max_cap,
+                                   live_lo, buf, enc_off, keep,
+                                   0).ins_off[-1])
+    k = max(max_ins, 1)
+    r = Inserted()
+    r.rc = np.zeros(max(T, 1), dtype=np.int32)
+    r.consumed, r.out_first, r.cap, r.live_lo = (
+        np.zeros(max(T, 1), dtype=np.uint32) for _ in range(4))
+    r.ins_off, out_ent = (np.zeros(T + 1, dtype=np.uint32) for _ in range(2))
+    r.chunk_cap = np.zeros(max(2 * T, 1), dtype=np.uint32)
+    r.strs = np.zeros(32 * k, dtype=np.uint8)
+    r.root, r.ins_cap = (np.zeros(2 * k, dtype=np.uint32) for _ in range(2))
+    r.ins_ref, r.ins_lo = (np.zeros(k, dtype=np.uint32) for _ in range(2))
+    r.ins_kind = np.zeros(k, dtype=np.uint8)
+    wire = max(int(enc_off[-1]) - int(enc_off[0]), 0) if T else 0
+    arena = int(keep_t[1][2 * D]) if D else 0
+    bound = tabs_insert_bound(arena, wire, max_ins,
+                              _tabs_longest(tables or ()))
+    out = np.full(min(bound, 1 << 32), 0xA5, dtype=np.uint8)
+    out_off = np.zeros(2 * (D + max_ins) + 1, dtype=np.uint32)
+    kp = _opt_u32(keep)
+    st = InsState(_np_ptr(cap), _np_ptr(max_cap), _np_ptr(live_lo), 0, 0)
+    sc = InsScan(_np_ptr(r.rc), _np_ptr(r.consumed), _np_ptr(r.ins_off),
+                 _np_ptr(r.chunk_cap), _np_ptr(r.strs), _np_ptr(r.root),
+                 _np_ptr(r.ins_cap), _np_ptr(r.ins_ref), _np_ptr(r.ins_kind),
+                 max_ins)
+    o = InsOut(_np_ptr(r.ins_lo), _np_ptr(out), _np_ptr(out_off),
+               _np_ptr(out_ent), _np_ptr(r.out_first), _np_ptr(r.cap),
+               _np_ptr(r.live_lo), len(out), D + max_ins)
+    r.ret = fn(*ctx, C.byref(t), C.byref(st),
+               _np_ptr(buf) if len(buf) else None, _np_ptr(enc_off),
+               _opt_ptr(kp), C.byref(sc), C.byref(o))
+    r.out_raw = out
+    if r.ret == EINVAL:
+        return r
+    n = min(int(r.ins_off[-1]), max_ins)
+    r.rc, r.consumed = r.rc[:T], r.consumed[:T]
+    r.chunk_cap = r.chunk_cap[:2 * T]
+    r.strs, r.root, r.ins_cap = r.strs[:32 * n], r.root[:2 * n], \
+        r.ins_cap[:2 * n]
+    r.ins_ref, r.ins_kind, r.ins_lo = r.ins_ref[:n], r.ins_kind[:n], \
+        r.ins_lo[:n]
+    if r.ret == ERANGE:
+        r.ins_lo = r.cap = r.live_lo = None
+        return r
+    if r.ret != OK:
+        raise QhuffError("%s failed: %d" % (what, r.ret))
+    r.cap, r.live_lo, r.out_first = r.cap[:T], r.live_lo[:T], r.out_first[:T]
+    De = int(out_ent[-1])
+    off = out_off[:2 * De + 1]
+    r.tables = ((out[:off[-1]], off, out_ent, r.out_first,
+                 u32(tables[4])) if T else ())
+    return r
+
+
+def tabs_insert_cpu(tables, cap, max_cap, live_lo, buf, enc_off, keep=None,
+                    max_ins=None):
+    """qhuff_tabs_insert_cpu: chunk c of buf (enc_off uint32 [T + 1]) applied
+    to table c of `tables` = (data, off, ent, first, max_entries) in the state
+    cap / max_cap / live_lo uint32 [T]; keep uint32 [T] or None -> Inserted.
+    max_ins None: the call is made twice, first with max_ins = 0 for the count
+    (the host form then uploads twice: pass max_ins where that matters).
+    r.out_raw is the whole out_bytes buffer, preset to 0xA5."""
+    return _tabs_insert(lib().qhuff_tabs_insert_cpu, (), "qhuff_tabs_insert_cpu",
+                        tables, cap, max_cap, live_lo, buf, enc_off, keep,
+                        max_ins)
 
 
 def hstrs_array(strs):
@@ -1917,6 +2057,31 @@ class Codec:
         res = (ret, hdr_off, rc[:m], kind[:n], sid[:n], hf[:n], did[:n],
                out[:off[2 * n]], off[:2 * n + 1], status[:2 * n])
         return res + ((h1[:n], h2[:n]) if hashes else ())
+
+    def tabs_insert_host(self, tables, cap, max_cap, live_lo, buf, enc_off,
+                         keep=None, max_ins=None):
+        """qhuff_tabs_insert_host over host arrays -> as tabs_insert_cpu."""
+        return _tabs_insert(lib().qhuff_tabs_insert_host, (self._ctx,),
+                            "qhuff_tabs_insert_host", tables, cap, max_cap,
+                            live_lo, buf, enc_off, keep, max_ins)
+
+    def scan_inserts_tabs(self, tabs, state, buf, enc_off, scan, stream=None):
+        """qhuff_scan_inserts_tabs: tabs a DynTables, state an InsState, scan
+        an InsScan, all of device pointers; buf, enc_off device tensors."""
+        r = lib().qhuff_scan_inserts_tabs(
+            self._ctx, C.byref(tabs), C.byref(state), buf.data_ptr(),
+            enc_off.data_ptr(), C.byref(scan), self._stream(stream))
+        self._check(r, "qhuff_scan_inserts_tabs")
+
+    def apply_inserts_tabs(self, tabs, state, buf, wire_bytes, keep, scan,
+                           n_ins, out, stream=None):
+        """qhuff_apply_inserts_tabs: as scan_inserts_tabs, keep a device
+        tensor or None, out an InsOut of device pointers."""
+        r = lib().qhuff_apply_inserts_tabs(
+            self._ctx, C.byref(tabs), C.byref(state), buf.data_ptr(),
+            wire_bytes, keep.data_ptr() if keep is not None else None,
+            C.byref(scan), n_ins, C.byref(out), self._stream(stream))
+        self._check(r, "qhuff_apply_inserts_tabs")
 
     def dyn_lookup_tabs_into(self, data, off, n, sec_hdr, m, tabs, sec_tab,
                              sec_win, name_hash, nameval_hash, kind,
